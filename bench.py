@@ -9,6 +9,12 @@ A "step" = one evaluate_population pass: device flatten + schedule + fused RK4 k
 all-gather of fitness.  Multi-GPU: one process per GPU (torchrun), weak scaling (8192
 individuals per rank), the only collective is the fitness all-gather (RCCL).
 
+A plain run sets up, warms up, times --steps steps and prints the result line (kernel_ms and the
+algorithmic-bytes roofline come from the timed steps' own HIP events).  --full adds the legs that
+take runs of their own: rocprofv3 PMC passes (roofline traffic / valu_frac), the end-to-end
+evaluate_population and evolve timing, the CPU baseline and the build record.  --dump-outputs DIR
+writes what the last timed step returned (dump_outputs).
+
 Other BASELINE configs (not the driver's line; for DESIGN.md): --config c2 (Acrobot static
 policy, pop 1024, 1 tree, depth <= 4, 16 rollouts) and --config c5 (64-dim SR "neural ODE":
 64 trees, max_nodes 128, depth <= 16, 8 rollouts, RK4 h = 0.01 x 200, pop 4096 per GPU =
@@ -56,14 +62,27 @@ def parse():
                     help="process group for N > 1: nccl (= RCCL, the product) or gloo -- a rehearsal of the "
                          "multi-rank flow (barriers, fitness all-gather, max-over-ranks timing) with several "
                          "ranks on one GPU, which RCCL refuses; never a measurement")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the legs that take runs of their own: the rocprofv3 PMC "
+                         "passes, the end-to-end evaluate_population / evolve timing, the CPU baseline and the build "
+                         "record (each with its own switch below); a plain run prints the headline line only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step returned as DIR/<name>.npy (float32): "
+                         "fitness whole, the trajectories (xs, ys, us, acts as [S, c, lanes]) on a fixed seeded sample "
+                         "of the P*R lanes, at most 64 MB in all; every file is finite: <name>.npy holds 0 where a "
+                         "blown-up candidate left inf / NaN and <name>_nonfinite.npy the class there (0 finite, 1 "
+                         "+inf, -1 -inf, 2 NaN); the workload is seeded, so equal arguments give equal inputs")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--no-pmc", action="store_true",
-                    help="skip the live rocprofv3 PMC passes (HBM traffic, VALU issue) of the dominant kernel")
+                    help="with --full: skip the live rocprofv3 PMC passes (HBM traffic, VALU issue) of the dominant "
+                         "kernel")
     ap.add_argument("--e2e-steps", type=int, default=20,
-                    help="timed GeneticProgramming.evaluate_population calls from host numpy (H2D + flatten + "
-                         "kernel + all-gather + D2H; SURVEY §8(d) end-to-end); 0 skips")
+                    help="with --full: timed GeneticProgramming.evaluate_population calls from host numpy (H2D + "
+                         "flatten + kernel + all-gather + D2H; SURVEY §8(d) end-to-end); 0 skips")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
     apply_config_defaults(a)
     return a
 
@@ -293,6 +312,42 @@ def end_to_end(args, ff, lib, data, pop, ws, rank, dev):
     return el * 1e3 / args.e2e_steps, fit, float(np.median(ev[1:]))
 
 
+DUMP_TRAJ_BYTES = 24 << 20  # the trajectory sample's values in --dump-outputs; with the equally large
+#                             <name>_nonfinite files and the whole vectors the dump stays under 64 MB
+
+
+def dump_outputs(path, res, fit, P, R):
+    """--dump-outputs: what the last timed step handed back, as float32 .npy files.  fitness (the
+    all-gathered vector) and the Dopri5 step attempts are written whole; the trajectory tensors,
+    indexed [S, c, P*R], keep the same sorted sample of lanes (numpy PCG64, seed 0, a function of
+    P*R and the bytes per lane only), so two builds run with equal arguments write the same
+    elements.
+    A candidate that blows up leaves +-inf / NaN in its trajectories (as the reference's solve
+    does), so every array is written as two all-finite files that together hold it exactly:
+    <name>.npy with 0 at each non-finite element, and <name>_nonfinite.npy with that element's
+    class there (0 finite, 1 +inf, -1 -inf, 2 NaN)."""
+    import torch
+    os.makedirs(path, exist_ok=True)
+    arrays = {"fitness": torch.as_tensor(fit).detach().cpu().numpy()}
+    if "steps" in res:
+        arrays["steps"] = res["steps"].cpu().numpy()
+    traj = [k for k in ("xs", "ys", "us", "acts") if k in res]
+    if traj:
+        lane_bytes = sum(res[k].shape[0] * res[k].shape[1] * 4 for k in traj)
+        n = min(P * R, max(1, DUMP_TRAJ_BYTES // lane_bytes))
+        lanes = np.sort(np.random.default_rng(0).choice(P * R, n, replace=False))
+        idx = torch.from_numpy(lanes).to(res[traj[0]].device)
+        for k in traj:
+            arrays[k] = res[k].index_select(2, idx).cpu().numpy()
+    for k, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        finite = np.isfinite(a)
+        kind = np.zeros_like(a)
+        kind[np.isposinf(a)], kind[np.isneginf(a)], kind[np.isnan(a)] = 1, -1, 2
+        np.save(os.path.join(path, f"{k}.npy"), np.where(finite, a, np.float32(0)))
+        np.save(os.path.join(path, f"{k}_nonfinite.npy"), kind)
+
+
 def build_record() -> dict:
     """Which kernel library this line measured: the in-tree libmtgp_hip.so, its size / mtime / hash
     prefix, and whether __graft_entry__.build() would have recompiled it (a source newer than the
@@ -381,6 +436,8 @@ def main():
     kernel_ms = list(hist)
 
     d = eng.prepare_data(data)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, res, fit, P, d["R"])
     R, S, n_steps = d["R"], d["n_save"], d["n_steps"]
     steps_host = res["steps"].cpu().numpy() if adaptive else None
     if adaptive:  # step attempts of this rank; every rank evaluates its own shard of the same size
@@ -408,7 +465,7 @@ def main():
     achieved_ys = alg_bytes / (kmean / 1e3) / 1e9
     traffic = valu = None
     pmc = None
-    if rank == 0 and ws == 1 and not args.no_pmc:
+    if args.full and rank == 0 and ws == 1 and not args.no_pmc:
         kname = {"c3": "k_ctl_dynamic", "c2": "k_ctl_static", "c5": "k_sr_wide"}[args.config]
         if adaptive:
             kname = "k_ctl_dopri5"
@@ -473,7 +530,8 @@ def main():
                                                                            "SQ_WAVES", "GRBM_GUI_ACTIVE")
                                                       if k in pmc}},
     }
-    out["build"] = build_record()
+    if args.full:
+        out["build"] = build_record()
     if ws > 1 and not rccl:
         out["rehearsal"] = "gloo process group, ranks sharing GPUs: a check of the multi-rank flow, not a measurement"
     if adaptive:
@@ -481,7 +539,7 @@ def main():
                          "attempt, rejected ones included)")
         out["config"]["ode_steps"] = units_per_step / (P * R * ws)  # mean attempts per rollout
         out["config"]["solver"] = "dopri5"
-    if args.e2e_steps > 0:
+    if args.full and args.e2e_steps > 0:
         e2e_ms, e2e_fit, evolve_ms = end_to_end(args, ff, lib, data, pop, ws, rank, dev)
         ok = bool(np.array_equal(e2e_fit.reshape(-1)[:P].view(np.uint32), res["fitness"].cpu().numpy().view(np.uint32)))
         units = (units_per_step if not adaptive else float("nan"))
@@ -495,7 +553,7 @@ def main():
             "host_evolve_ms": evolve_ms,
             "host_evolve_what": f"GeneticProgramming.evolve of the {P * ws}-candidate population (native host "
                                 f"library on {host_evolve_threads()} threads), median of 3"}
-    if rank == 0 and ws == 1 and not args.no_cpu_baseline:  # (the contract: rank 0 at N = 1 only)
+    if args.full and rank == 0 and ws == 1 and not args.no_cpu_baseline:  # (the contract: rank 0 at N = 1 only)
         out["cpu_baseline"] = cpu_baseline(args, lib, ff, data, pop, steps_host)
     if rank == 0:
         print(json.dumps(out), flush=True)

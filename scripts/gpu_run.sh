@@ -3,7 +3,7 @@
 # Outputs land in gpurun_out/TAG/ (merged back by gpurun).
 #   test        python -m pytest tests -m gpu (whole GPU suite)
 #   smoke       __graft_entry__.smoke()
-#   bench_c3    python bench.py (the driver's line: C3, PMC + CPU baseline + end-to-end)
+#   bench_c3    python bench.py --full (the driver's line: C3, PMC + CPU baseline + end-to-end)
 #   bench_c2 / bench_c5 / bench_dp / bench_dpn   other configs (dp = C3 Dopri5, dpn = + obs_noise 0.1)
 #   prof_c3 / prof_c2 / prof_c5 / prof_dp / prof_dpn   rocprofv3 --kernel-trace --stats of kprof (30 evaluations)
 set -o pipefail
@@ -59,18 +59,18 @@ for step in "$@"; do
     gradtime) run gradtime 300 python scripts/grad_time.py || exit 1 ;;
     prof_grad) run prof_grad 300 rocprofv3 --kernel-trace --stats -d $O/prof_grad -o prof_grad -- python3 scripts/grad_time.py || exit 1
                python3 scripts/kstats_db.py $(find $O/prof_grad -name "*.db" | head -1) $O/prof_grad_kernel_stats.csv; head -8 $O/prof_grad_kernel_stats.csv ;;
-    c5occ) run c5occ_2 300 python bench.py --config c5 --no-cpu-baseline --e2e-steps 0 || exit 1
-           run c5occ_1 300 env MTGP_WIDE_LDS_MIN=90000 python bench.py --config c5 --no-cpu-baseline --e2e-steps 0 || exit 1
-           run c5occ_2b 300 env MTGP_WIDE_LDS_MIN=60000 python bench.py --config c5 --no-cpu-baseline --e2e-steps 0 || exit 1 ;;
+    c5occ) run c5occ_2 300 python bench.py --full --config c5 --no-cpu-baseline --e2e-steps 0 || exit 1
+           run c5occ_1 300 env MTGP_WIDE_LDS_MIN=90000 python bench.py --full --config c5 --no-cpu-baseline --e2e-steps 0 || exit 1
+           run c5occ_2b 300 env MTGP_WIDE_LDS_MIN=60000 python bench.py --full --config c5 --no-cpu-baseline --e2e-steps 0 || exit 1 ;;
     testsched) run pytest_sched 600 python -u -m pytest tests/test_gpu_schedule.py tests/test_gpu_build.py tests/test_gpu_parity.py -m gpu -x -v --timeout 300 --timeout-method thread || exit 1 ;;
     testrccl) run pytest_rccl 300 python -u -m pytest tests/test_gpu_rccl.py -m gpu -x -v --timeout 240 --timeout-method thread || exit 1 ;;
     testbuild) run pytest_build 300 python -u -m pytest tests/test_gpu_build.py -m gpu -x -v --timeout 120 --timeout-method thread || exit 1 ;;
     testext) run pytest_ext 600 python -u -m pytest tests/test_gpu_ext_ops.py tests/test_gpu_build.py -m gpu -x -v --timeout 300 --timeout-method thread || exit 1 ;;
-    bench_ss8) run bench_ss8 600 python bench.py --state-size 8 --steps 30 --warmup 5 --e2e-steps 0 || exit 1 ;;
-    bench_ss12) run bench_ss12 600 python bench.py --state-size 12 --steps 20 --warmup 3 --e2e-steps 0 --no-cpu-baseline || exit 1 ;;
+    bench_ss8) run bench_ss8 600 python bench.py --full --state-size 8 --steps 30 --warmup 5 --e2e-steps 0 || exit 1 ;;
+    bench_ss12) run bench_ss12 600 python bench.py --full --state-size 12 --steps 20 --warmup 3 --e2e-steps 0 --no-cpu-baseline || exit 1 ;;
     teststate) run pytest_state 600 python -u -m pytest tests/test_gpu_parity.py -m gpu -x -v -k state_size --timeout 300 --timeout-method thread || exit 1 ;;
-    bench_c3q) run bench_c3q 300 python bench.py --no-cpu-baseline --e2e-steps 0 || exit 1 ;;
-    bench_c3ext) run bench_c3ext 300 python bench.py --ext-ops --no-cpu-baseline --e2e-steps 0 || exit 1 ;;
+    bench_c3q) run bench_c3q 300 python bench.py --full --no-cpu-baseline --e2e-steps 0 || exit 1 ;;
+    bench_c3ext) run bench_c3ext 300 python bench.py --full --ext-ops --no-cpu-baseline --e2e-steps 0 || exit 1 ;;
     dbgcheck) run dbgcheck 600 env MTGP_LIB=multitreegp_amd/lib/dbg/libmtgp_hip_dbg.so python -u scripts/debug_store_check.py \
                 tests/test_gpu_acrobot_mask.py tests/test_gpu_cstep.py tests/test_gpu_parity.py || exit 1 ;;
     wavetime) run wavetime 300 env MTGP_LIB=multitreegp_amd/lib/dbg/libmtgp_hip_wt.so python -u scripts/wave_times.py --save $O/wavetime.npz || exit 1
@@ -83,11 +83,11 @@ for step in "$@"; do
     ab_fair_mode) run ab_fair_mode 500 python scripts/kvariants.py --config c3 --rounds 8 --variants "prod,prod@MTGP_FAIR_MODE=1,prod@MTGP_FAIR=9" --tag c3_fair_mode || exit 1 ;;
     ab_fair) run ab_fair 400 python scripts/kvariants.py --config c3 --rounds 8 --variants "prod,prod@MTGP_FAIR=1" --tag c3_fair || exit 1 ;;
     smoke) run smoke 180 python -c "import __graft_entry__ as g; g.smoke()" || exit 1 ;;
-    bench_c3) run bench_c3 600 python bench.py || exit 1 ;;
-    bench_c2) run bench_c2 600 python bench.py --config c2 || exit 1 ;;
-    bench_c5) run bench_c5 600 python bench.py --config c5 || exit 1 ;;
-    bench_dp) run bench_dp 600 python bench.py --solver dopri5 --steps 20 --warmup 3 || exit 1 ;;
-    bench_dpn) run bench_dpn 600 python bench.py --solver dopri5 --obs-noise 0.1 --steps 10 --warmup 2 || exit 1 ;;
+    bench_c3) run bench_c3 600 python bench.py --full || exit 1 ;;
+    bench_c2) run bench_c2 600 python bench.py --full --config c2 || exit 1 ;;
+    bench_c5) run bench_c5 600 python bench.py --full --config c5 || exit 1 ;;
+    bench_dp) run bench_dp 600 python bench.py --full --solver dopri5 --steps 20 --warmup 3 || exit 1 ;;
+    bench_dpn) run bench_dpn 600 python bench.py --full --solver dopri5 --obs-noise 0.1 --steps 10 --warmup 2 || exit 1 ;;
     prof_c3) prof prof_c3 c3 || exit 1 ;;
     prof_c3_w64) MTGP_JIT_EMIT=wave64 prof prof_c3_w64 c3 || exit 1 ;;
     prof_c3_fw) MTGP_FLAT_HALVES=0 prof prof_c3_fw c3 || exit 1 ;;
@@ -121,7 +121,7 @@ for step in "$@"; do
     ab_c2_fuse) run ab_c2_fuse 400 python scripts/kvariants.py --config c2 --rounds 10 --variants "prod,nofuse" --tag c2_fuse || exit 1 ;;
     ab_c2) V=prod; for f in multitreegp_amd/lib/abrun/libmtgp_hip_*.so; do b=$(basename $f .so); V=$V,${b#libmtgp_hip_}; done
       run ab_c2 400 python scripts/kvariants.py --config c2 --rounds 8 --variants $V --tag ab_c2 || exit 1 ;;
-    bench_gloo2) run bench_gloo2 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 2 --dist-backend gloo --steps 10 --warmup 2 --no-pmc --e2e-steps 3 || exit 1 ;;
+    bench_gloo2) run bench_gloo2 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 bench.py --full --gpus 2 --dist-backend gloo --steps 10 --warmup 2 --no-pmc --e2e-steps 3 || exit 1 ;;
     rccl2) run rccl2 180 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29531 scripts/rccl_two_ranks.py || exit 1 ;;
     ab_dp_layout) run ab_dp_layout 600 python scripts/kvariants.py --solver dopri5 --rounds 4 --variants "prod@MTGP_TRAJ_LAYOUT=time,prod" --tag dp_layout || exit 1 ;;
     ab_dpw3) run ab_dpw3 600 python scripts/kvariants.py --solver dopri5 --rounds 4 --variants "prod,dpw3" --tag dp_w3 && run ab_dpw3n 600 python scripts/kvariants.py --solver dopri5 --obs-noise 0.1 --rounds 2 --variants "prod,dpw3" --tag dpn_w3 || exit 1 ;;
