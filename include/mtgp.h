@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define MTGP_ABI_VERSION 20
+#define MTGP_ABI_VERSION 21
 
 /* ---------------------------------------------------------------- limits */
 #define MTGP_MAX_FUNCS 128   /* node functions 2 + K + V (gp.py:135-199)       */
@@ -443,13 +443,21 @@ int mtgp_sr_grad(const MtgpModel* model, const MtgpInstr* prog, int32_t n_prog, 
 /* ABI v16: the same for the dynamic and static control models (dynamic_evaluate.py:37-118,
  * feedforward_evaluate.py:36-110; value_and_grad of gp.py:253 / 435-452): every MTGP_ENV_*,
  * MTGP_SOLVER_RK4, MTGP_SOLVER_EULER or (ABI v17) MTGP_SOLVER_DOPRI5 (step sizes held at their
- * primal values, as mtgp_sr_grad), observation noise included, state_size <= 3, R <= 64.
+ * primal values, as mtgp_sr_grad), observation noise included, state_size <= 16, R <= 64.
  * The programs read the reference's data vector [y(n_obs), a, u, targets] (MtgpProgramSpec gap 0)
  * followed by the K parameter slots.  Tangent rules: include/mtgp_dual.h (the environment drift,
  * f_obs, clip); the argmax step of the Acrobot fitness (acrobot.py:79) is piecewise constant.
  * ABI v19: rollouts->fit_kof (the general Acrobot cost mask, ts off the one-pass grid) is
  * differentiated too; scratch must then hold P * K * R * 2 * (1 + n_save) floats (the lanes' cost
- * prefixes follow the partials). */
+ * prefixes follow the partials).
+ * ABI v21: wide states -- the dynamic model with state_size 4..16, or a data vector
+ * n_obs + state_size + 1 + n_targets of 9..24 slots (more: MTGP_ERR_ARG) -- run a kernel that keeps
+ * every per-lane array in LDS columns, one wave per workgroup: 512 bytes of dynamic LDS per slot,
+ * 8 + D + 7 (n_var + state_size) slots with a fixed-step solver and 8 + D + 13 (n_var +
+ * state_size) with Dopri5, i.e. up to 86 KB / 146 KB of the CU's 160 KB.  The call raises the
+ * kernel's dynamic-LDS limit (hipFuncSetAttribute) the first time a device runs it and returns
+ * MTGP_ERR_LAUNCH when the device refuses.  Results, scratch and every other limit are as for the
+ * narrow states. */
 int mtgp_ctl_grad(const MtgpModel* model, const MtgpInstr* prog, int32_t n_prog, int32_t L, int32_t P,
                   const float* theta, const int32_t* nparam, int32_t K, const MtgpRollouts* rollouts,
                   float* scratch, float* loss_out, float* grad_out, void* stream);
@@ -463,7 +471,9 @@ int mtgp_ctl_grad(const MtgpModel* model, const MtgpInstr* prog, int32_t n_prog,
  * [P * n_prog + 1]; info: device int32 [2], written by the call ([0] < 0: some program does not
  * translate, [1]: bytes the code needs).  When the code does not fit or a program does not
  * translate, the kernel interprets (same results, slower).  jit == NULL or jit->code == NULL:
- * exactly mtgp_ctl_grad. */
+ * exactly mtgp_ctl_grad.  ABI v21: wide states (mtgp_ctl_grad: state_size > 3 or a data vector
+ * over eight slots) always interpret -- the code is a register-data design -- and leave jit's
+ * buffers untouched; the call still returns MTGP_OK. */
 typedef struct {
   void* code;
   size_t code_bytes;

@@ -10,7 +10,8 @@ Every 5th generation after generation 10 the reference takes the 50 best candida
   (first minimum).
 
 Here the loss and gradient come from ``mtgp_sr_grad`` (the SR evaluator) and ``mtgp_ctl_grad``
-(the dynamic and static control evaluators, every environment; csrc/mtgp_grad.hip): forward-mode
+(the dynamic and static control evaluators, every environment, state_size <= 16;
+csrc/mtgp_grad.hip): forward-mode
 dual numbers through the same RK4 / Euler solve as the evaluator, one GPU lane per (candidate,
 parameter, rollout).  The parameters are the coefficient rows (``f == 1``) of every tree: the
 host turns the rows of one chunk into variable rows that read data slots ``n_data + k`` (after
@@ -155,8 +156,10 @@ class CoefficientOptimiser:
         kind = getattr(ff, "solver_kind", "")
         if kind not in ("rk4", "euler", "dopri5"):
             raise NotImplementedError(f"coefficient optimisation: solver {kind!r}")
-        if ff.model_id != nat.MODEL_SR and getattr(ff, "state_size", 0) > 3:
-            raise NotImplementedError("coefficient optimisation of the dynamic evaluator: state_size <= 3")
+        # (ABI v21: the dynamic evaluator's own limit; its constructor refuses more)
+        if ff.model_id != nat.MODEL_SR and getattr(ff, "state_size", 0) > nat.GRAD_MAX_STATE:
+            raise NotImplementedError(f"coefficient optimisation of the dynamic evaluator: state_size <= "
+                                      f"{nat.GRAD_MAX_STATE}")
 
     @staticmethod
     def check_data(d: dict) -> None:
@@ -227,7 +230,12 @@ class CoefficientOptimiser:
             lo_d = torch.empty((B,), dtype=torch.float32, device=dev)
             gr_d = torch.empty((B, K), dtype=torch.float32, device=dev)
             called = grad_fn
-            if self.use_jit and (eng.ff.model_id != nat.MODEL_SR or n_data <= 4):
+            # dual-number code: the register-data kernels only (SR with n_var <= 4, control with
+            # state_size <= 3); wide dynamic states interpret from LDS columns (mtgp.h ABI v21)
+            wide = eng.ff.model_id != nat.MODEL_SR and getattr(eng.ff, "state_size", 0) > 3
+            if wide:
+                self.last_jit_info = None
+            if self.use_jit and not wide and (eng.ff.model_id != nat.MODEL_SR or n_data <= 4):
                 code, nbytes = eng.grad_code_buffer(nat.grad_jit_bytes(B, n_prog, L))
                 offs = torch.empty((B * n_prog + 1,), dtype=torch.int32, device=dev)
                 info = torch.empty((2,), dtype=torch.int32, device=dev)

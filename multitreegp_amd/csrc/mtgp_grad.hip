@@ -14,6 +14,7 @@
 // max_fitness replacement, the pairwise rollout sum of finish_group and jnp.clip's derivative.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <atomic>
 #include "mtgp.h"
 #include "mtgp_f32math.h"
 #include "mtgp_prng.h"
@@ -1213,6 +1214,441 @@ __global__ void __launch_bounds__(kGradBlock) k_ctl_grad(GradArgs A) {
   out[1] = dF;
 }
 
+// ------------------------------------------------------------------------------------------
+// k_ctl_grad for wide states: the dynamic model with a run-time state_size na = 4..16 (ND = NV + na
+// up to 20 components, a data vector [y, a, u, tg] of up to kWideData slots).  The register form
+// above cannot hold that (its RK4 arrays alone would be ~280 floats per lane), so every per-lane
+// array -- the dual state, the stage / accumulator arrays, the data vector and the operand stack --
+// is a column of the block's dynamic LDS, lane-minor: slot i of a lane at col[i * kWideBlock], an
+// 8-byte Dual per lane, so consecutive lanes hit consecutive banks and a run-time component index
+// costs nothing.  One wave per workgroup (kWideBlock = 64): at ND = 20, D = 24 the RK4 form takes
+// 172 slots = 86 KB and the Dopri5 form 292 slots = 146 KB of the CU's 160 KB.  A lane only ever
+// touches its own column, so there is no barrier.  The arithmetic is k_ctl_grad's (and
+// oracle_ctl_grad's) operation for operation; the programs run through the dual interpreter (the
+// dual-number code of mtgp_jit_dual.h is a register-data design, D <= 8).
+constexpr int kWideBlock = 64;  // threads per block of the wide gradient kernel: one wave
+constexpr int kWideData = 24;   // data slots: n_obs 4 + state_size 16 + u + up to 3 targets
+constexpr int kWideState = 16;  // state_size ceiling (DynamicEvaluator's own)
+// LDS slots (Duals per lane) of one launch; the kernel lays its columns out in this order
+__host__ __device__ constexpr int wide_arrays(bool dp) { return dp ? 13 : 7; }
+__host__ __device__ constexpr int wide_slots(bool dp, int nd, int D) {
+  return MTGP_STACK_MAX + D + wide_arrays(dp) * nd;
+}
+struct WideCol {
+  Dual* c;  // &lds[first slot][threadIdx.x]
+  __device__ Dual& operator[](int i) const { return c[i * kWideBlock]; }
+  __device__ WideCol at(int i) const { return {c + (size_t)i * kWideBlock}; }
+};
+struct WideStack {
+  Dual* col;
+  __device__ Dual& at(int i) { return col[i * kWideBlock]; }
+};
+
+template <int ENV, bool DP>
+__global__ void __launch_bounds__(kWideBlock) k_ctl_grad_wide(GradArgs A) {
+  extern __shared__ Dual w_lds[];
+  constexpr int NV = CtlEnv<ENV>::NV, NP = CtlEnv<ENV>::NP;
+  const int R = A.ro.R;
+  int p, k, r;
+  size_t slot;
+  if (!grad_lane(A, p, k, r, slot)) return;
+  float* out = A.part + slot * 2;
+  const int np = A.nparam[p];
+  if (k > 0 && k >= np) {
+    out[0] = 0.0f;
+    out[1] = 0.0f;
+    return;
+  }
+  const int kk = k < np ? k : -1;
+  const float* th = A.theta + (size_t)p * A.K;
+  const int no = A.m.n_obs, nt = A.m.n_targets, na = A.m.state_size;
+  const int ND = NV + na, D = no + na + 1 + nt;
+  const MtgpInstr* pr = A.prog + (size_t)p * A.n_prog * A.L;
+  const MtgpInstr* p_read = pr + (size_t)A.m.prog_readout * A.L;
+  const MtgpInstr* p_save = pr + (size_t)A.m.prog_readout_save * A.L;
+  const MtgpInstr* p_state = pr + (size_t)A.m.prog_state * A.L;
+  // the columns of this lane: operand stack, data vector, then the solver's ND-slot arrays
+  const WideCol lds{w_lds + threadIdx.x};
+  const WideStack stk{lds.c};
+  const WideCol dv = lds.at(MTGP_STACK_MAX);
+  const WideCol arr = dv.at(D);
+  auto col = [&](int a) { return arr.at(a * ND); };
+  float prm[NP], tg[8];
+#pragma unroll
+  for (int i = 0; i < NP; ++i) prm[i] = A.ro.params[(size_t)r * NP + i];
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    tg[i] = 0.0f;
+    if (i < nt) tg[i] = A.ro.targets[(size_t)r * nt + i];
+  }
+  const uint32_t* key = A.ro.obs_keys ? A.ro.obs_keys + 2 * (size_t)r : nullptr;
+  // the data vector's reader: a run-time-indexed LDS slot, or a parameter
+  auto V = [&](uint32_t off) -> Dual {
+    const int sl = (int)(off / MTGP_SLOT_BYTES);
+    if (sl < D) return dv[sl];
+    return {th[sl - D], (sl - D == kk) ? 1.0f : 0.0f};
+  };
+  auto put_targets = [&]() {
+#pragma unroll
+    for (int j = 0; j < 8; ++j)
+      if (j < nt) dv[no + na + 1 + j] = {tg[j], 0.0f};
+  };
+  // f_obs (cbase.py:43-48, acrobot.py:29-32) in duals: k_ctl_grad's, reading the environment's
+  // NV components from the state column
+  auto f_obs = [&](float t, const WideCol x, Dual* y) {
+    float nz[NV];
+#pragma unroll
+    for (int j = 0; j < NV; ++j) nz[j] = 0.0f;
+    if (key) {
+      uint32_t n0, n1;
+      mtgp_fold_in(key[0], key[1], mtgp_f2u(t), &n0, &n1);
+      float n[NV];
+#pragma unroll
+      for (int i = 0; i < NV; ++i)
+        n[i] = i < no ? mtgp_normal_from_bits(mtgp_random_bits_word(n0, n1, i, no, A.m.prng_impl)) : 0.0f;
+#pragma unroll
+      for (int j = 0; j < NV; ++j) {
+        if (j >= no) continue;
+        float sacc = n[0] * A.ro.obs_w[0 * no + j];
+#pragma unroll
+        for (int i = 1; i < NV; ++i)
+          if (i < no) sacc = sacc + n[i] * A.ro.obs_w[i * no + j];
+        nz[j] = sacc;
+      }
+    }
+    Dual xe[NV];
+#pragma unroll
+    for (int i = 0; i < NV; ++i) xe[i] = x[i];
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+      if (i >= no) { y[i] = {0.0f, 0.0f}; continue; }
+      MtgpDual sacc = mtgp_dl_cmul(i == 0 ? 1.0f : 0.0f, tod(xe[0]));
+#pragma unroll
+      for (int j = 1; j < NV; ++j) sacc = mtgp_dl_add(sacc, mtgp_dl_cmul(i == j ? 1.0f : 0.0f, tod(xe[j])));
+      y[i] = frd(mtgp_dl_addc(sacc, nz[i]));
+    }
+    if (ENV == 0) {
+      y[0] = frd(mtgp_dl_wrap_angle(tod(y[0])));
+      if (no > 1) y[1] = frd(mtgp_dl_wrap_angle(tod(y[1])));
+    }
+  };
+  // _drift (dyn.py:107-118) in duals: the readout on [0, a, 0, tg], the state programs on
+  // [y, a, u, tg], then the environment drift (it reads only the state and u)
+  auto rhs = [&](float t, const WideCol st, const WideCol ds) {
+    Dual y[NV];
+    f_obs(t, st, y);
+    for (int j = 0; j < D; ++j) dv[j] = {0.0f, 0.0f};
+    for (int j = 0; j < na; ++j) dv[no + j] = st[NV + j];
+    put_targets();
+    const Dual u = run_dual_src(p_read, V, stk);
+#pragma unroll
+    for (int i = 0; i < NV; ++i)
+      if (i < no) dv[i] = y[i];
+    dv[no + na] = u;
+#pragma unroll 1
+    for (int j = 0; j < na; ++j) ds[NV + j] = run_dual_src(p_state + (size_t)j * A.L, V, stk);
+    MtgpDual xx[NV], d[NV];
+#pragma unroll
+    for (int i = 0; i < NV; ++i) xx[i] = tod(st[i]);
+    if constexpr (ENV == 0) mtgp_dl_acro_drift(prm, xx, tod(u), d);
+    else if constexpr (ENV == 1) mtgp_dl_ho_drift(prm, xx, tod(u), d);
+    else mtgp_dl_reactor_drift(prm, xx, tod(u), d);
+#pragma unroll
+    for (int i = 0; i < NV; ++i) ds[i] = frd(d[i]);
+  };
+  // online fitness over the save points: k_ctl_grad's, addition for addition
+  const int S = A.m.n_save;
+  const float* ts = A.ro.ts;
+  const float dts = ts[1] - ts[0];
+  bool settled = false;
+  int fs = 0;
+  MtgpDual cs = mtgp_dl(0.0f, 0.0f), c0 = mtgp_dl(0.0f, 0.0f);
+  // the general Acrobot mask (MtgpRollouts.fit_kof), see k_ctl_grad
+  const int32_t* kof = ENV == 0 ? A.ro.fit_kof : nullptr;
+  const size_t nsl = (size_t)A.P * A.K * R;
+  MtgpDual pre = mtgp_dl(0.0f, 0.0f), AK = mtgp_dl(0.0f, 0.0f);
+  int Kt = -1, q_pre = -1;
+  bool a_set = false;
+  auto hist_put = [&](int q, MtgpDual v) {
+    float* h = A.hist + ((size_t)q * nsl + slot) * 2;
+    h[0] = v.v;
+    h[1] = v.d;
+  };
+  auto hist_get = [&](int q) {
+    const float* h = A.hist + ((size_t)q * nsl + slot) * 2;
+    return mtgp_dl(h[0], h[1]);
+  };
+  auto prefix_done = [&]() {
+    if (Kt == 0) { AK = mtgp_dl(0.0f, 0.0f); a_set = true; }
+    else if (Kt - 1 <= q_pre) { AK = Kt - 1 == q_pre ? pre : hist_get(Kt - 1); a_set = true; }
+  };
+  auto save_point = [&](int q, const WideCol xq) {
+    Dual y[NV];
+    f_obs(ts[q], xq, y);
+    for (int j = 0; j < D; ++j) dv[j] = {0.0f, 0.0f};
+#pragma unroll
+    for (int i = 0; i < NV; ++i)
+      if (i < no) dv[i] = y[i];
+    for (int j = 0; j < na; ++j) dv[no + j] = xq[NV + j];
+    put_targets();
+    const Dual u = run_dual_src(p_save, V, stk);  // dyn.py:101 [y, a, 0, tg]
+    const Dual x0q = xq[0], x1q = xq[1];
+    if constexpr (ENV == 0) {
+      const MtgpDual ud = tod(u);
+      const MtgpDual cost = mtgp_dl_mul(mtgp_dl_mulc(ud, 0.01f), ud);
+      const bool reached = ((-mtgp_cosf(x0q.v)) - mtgp_cosf(x0q.v + x1q.v)) > 1.5f;
+      if (kof) {
+        if (!settled || !a_set) {  // fold c_q into the prefix while it may still be needed
+          pre = mtgp_dl_add(q == 0 ? mtgp_dl(0.0f, 0.0f) : pre, cost);
+          q_pre = q;
+          if (!settled) hist_put(q, pre);
+        }
+        if (!settled && reached) {
+          settled = true;
+          fs = q;
+          Kt = kof[fs];
+        }
+        if (settled && !a_set) prefix_done();
+        return;
+      }
+      if (q == 0) {
+        const bool incl0 = !((ts[0] / dts) > 0.0f);
+        c0 = mtgp_dl_add(mtgp_dl(0.0f, 0.0f), incl0 ? cost : mtgp_dl(0.0f, 0.0f));
+        cs = mtgp_dl_add(mtgp_dl(0.0f, 0.0f), cost);
+        if (reached) { settled = true; fs = 0; cs = c0; }
+      } else if (settled) {
+        cs = mtgp_dl_add(cs, mtgp_dl(0.0f, 0.0f));
+      } else if (reached) {
+        fs = q;
+        cs = mtgp_dl_add(cs, ((ts[q] / dts) > (float)q) ? mtgp_dl(0.0f, 0.0f) : cost);
+        settled = true;
+      } else {
+        cs = mtgp_dl_add(cs, cost);
+      }
+    } else if constexpr (ENV == 1) {
+      const float Q[4] = {0.5f, 0.0f, 0.0f, 0.0f};
+      const float ud0 = (-0.0f * 0.0f + -1.0f * (-prm[0])) * tg[0] + ((-0.0f) * 1.0f + (-1.0f) * (-prm[1])) * 0.0f;
+      const MtgpDual e[2] = {mtgp_dl_subc(tod(x0q), tg[0]), mtgp_dl_subc(tod(x1q), 0.0f)};
+      const MtgpDual du = mtgp_dl_subc(tod(u), ud0);
+      cs = mtgp_dl_add(cs, mtgp_dl_add(mtgp_dl_quad_form(e, Q, 2), mtgp_dl_mul(mtgp_dl_mulc(du, 0.5f), du)));
+    } else {
+      const float Q[9] = {0.0f, 0.0f, 0.0f, 0.0f, 0.01f, 0.0f, 0.0f, 0.0f, 0.0f};
+      const Dual x2q = xq[2];
+      const MtgpDual e[3] = {mtgp_dl_subc(tod(x0q), 0.0f), mtgp_dl_subc(tod(x1q), tg[0]),
+                             mtgp_dl_subc(tod(x2q), 0.0f)};
+      cs = mtgp_dl_add(cs, mtgp_dl_add(mtgp_dl_quad_form(e, Q, 3), mtgp_dl_mul(mtgp_dl_mulc(tod(u), 0.0001f), tod(u))));
+    }
+  };
+  auto bad = [&](const WideCol st) {  // cond_fn (acrobot.py:86-87; the others: any non-finite)
+    bool b = false;
+    for (int i = 0; i < ND; ++i) b = b || !mtgp_isfinite(st[i].v);
+    if (ENV == 0) {
+      const float v2 = st[2].v, v3 = st[3].v;
+      b = b || (!mtgp_isnan(v2) && __builtin_fabsf(v2) > MTGP_8PI_F);
+      b = b || (!mtgp_isnan(v3) && __builtin_fabsf(v3) > MTGP_18PI_F);
+    }
+    return b;
+  };
+  const WideCol s = col(0);
+  for (int i = 0; i < ND; ++i) s[i] = {i < NV ? A.ro.x0[(size_t)r * NV + i] : 0.0f, 0.0f};
+  bool prev_ok = !bad(s);
+  const float h = A.m.h;
+  int q_saved = 0;
+  WideCol fill = s;  // a column free after the solve, for the +inf fill saves of the general mask
+  if constexpr (DP) {
+    save_point(0, s);
+    // k_ctl_grad's Dopri5 solve: the tableau sums accumulated as the stages arrive (each sum's
+    // ascending-j order of mtgp_dp_term), step sizes / accept / reject / event primal
+    const float t_end = ts[S - 1];
+    const WideCol f0 = col(1), fc = col(2), yi = col(3), sk = col(4), am = col(5), ae = col(6);  // ae: .v only
+    auto ac = [&](int q) { return col(7 + q); };  // ac(i - 1): stage i's sum
+    fill = sk;
+    auto contrib = [&](int j, const WideCol f) __attribute__((always_inline)) {
+      const bool first = j == 0;
+      const float we = kDpE[j], wm = kDpCM[j];
+      for (int i = 0; i < ND; ++i) {
+        const Dual fi = f[i];
+#pragma unroll
+        for (int q = 0; q < 6; ++q) {
+          if (q + 1 <= j) continue;  // stages up to j are done
+          const float w = kDpA[q + 1][j];
+          const Dual a = ac(q)[i];
+          ac(q)[i] = {mtgp_dp_term(a.v, w, fi.v, first), mtgp_dp_term(a.d, w, fi.d, first)};
+        }
+        const Dual m = am[i];
+        ae[i].v = mtgp_dp_term(ae[i].v, we, fi.v, first);
+        am[i] = {mtgp_dp_term(m.v, wm, fi.v, first), mtgp_dp_term(m.d, wm, fi.d, first)};
+      }
+    };
+    int ks = 1, steps = 0;
+    float t = ts[0];
+    float tnext = t + h;
+    tnext = tnext > t_end ? t_end : tnext;
+    bool have_f0 = false;  // f_0 of the first attempt comes from the stage loop (one rhs site)
+    const MtgpDpPid pid = A.m.pid_custom ? MtgpDpPid{A.m.pid_c1, A.m.pid_c2, A.m.pid_c3, A.m.pid_safety,
+                                                     A.m.pid_factormin, A.m.pid_factormax}
+                                         : MtgpDpPid MTGP_DP_PID_DEFAULT;
+    MtgpDpCtl ctl{1.0f, 1.0f, 0};
+    const int force_dtmin = !A.m.no_force_dtmin;
+    while (t < t_end && steps < A.m.max_steps) {
+      const float hs = tnext - t;
+      if (have_f0) contrib(0, f0);
+#pragma unroll 1
+      for (int st = have_f0 ? 1 : 0; st <= 6; ++st) {
+        if (st == 0) {
+          for (int i = 0; i < ND; ++i) yi[i] = s[i];
+        } else {
+          const WideCol a = ac(st - 1);
+          for (int i = 0; i < ND; ++i) {
+            const Dual ai = a[i], si = s[i];
+            yi[i] = Dual{MTGP_FMAF(hs, ai.v, si.v), MTGP_FMAF(hs, ai.d, si.d)};
+          }
+        }
+        rhs(st == 0 ? t : t + mtgp_dp_c(st) * hs, yi, fc);
+        if (st == 0) {
+          for (int i = 0; i < ND; ++i) f0[i] = fc[i];
+          have_f0 = true;
+        }
+        contrib(st, fc);
+      }
+      // yi = y1 (stage 6's input), fc = f_6
+      float msum = 0.0f;
+      for (int i = 0; i < ND; ++i) {
+        const float sc = mtgp_dp_scaled(hs * ae[i].v, s[i].v, yi[i].v, A.m.rtol, A.m.atol);
+        msum = (i == 0) ? sc * sc : msum + sc * sc;
+      }
+      const float ms = msum / (float)ND;
+      int keep, fail;
+      const float dt = mtgp_dp_control(ms, hs, A.m.dtmin, A.m.dtmax, force_dtmin, &pid, &ctl, &keep, &fail);
+      ++steps;
+      bool stop = fail != 0;
+      if (keep) {
+        const float t1 = tnext;
+        while (ks < S && ts[ks] <= t1) {
+          const float thq = (ts[ks] - t) / hs;
+          for (int i = 0; i < ND; ++i) {
+            const Dual si = s[i], y1i = yi[i], mi = am[i], f0i = f0[i], fci = fc[i];
+            const float ymid = MTGP_FMAF(hs, mi.v, si.v), dymid = MTGP_FMAF(hs, mi.d, si.d);
+            sk[i] = {mtgp_dp_interp(si.v, y1i.v, ymid, hs * f0i.v, hs * fci.v, thq),
+                     mtgp_dp_interp(si.d, y1i.d, dymid, hs * f0i.d, hs * fci.d, thq)};
+          }
+          save_point(ks, sk);
+          ++ks;
+        }
+        t = t1;
+        for (int i = 0; i < ND; ++i) {
+          s[i] = yi[i];
+          f0[i] = fc[i];  // FSAL
+        }
+        const bool ok = !bad(s);
+        if (prev_ok && !ok) stop = true;  // Event(cond_fn_nan), dyn.py:94
+        prev_ok = ok;
+      }
+      if (stop) break;
+      tnext = mtgp_dp_clip_end(t, dt, t_end, keep);
+    }
+    q_saved = ks - 1;
+  } else {
+    // k_ctl_grad's fixed-step solve (include/mtgp_cstep.h) in duals
+    const bool euler = A.m.solver == MTGP_SOLVER_EULER;
+    const float t_end = ts[S - 1];
+    float t = ts[0], tn = mtgp_cs_first_end(t, h, t_end);
+    int steps = 0, ks = 0;
+    // tmp: the stage input, then (the stages done) the dense-output point of a save
+    const WideCol f0 = col(1), y1 = col(2), tmp = col(3), kx = col(4), acc = col(5), z = col(6);
+    fill = tmp;
+    while (t < t_end && mtgp_cs_advancing(steps, t, tn) && (A.m.max_steps <= 0 || steps < A.m.max_steps)) {
+      const float dt = tn - t;
+      // the zero tableau entries' terms (mtgp_cstep.h) start every step at zero, as the oracle's do
+      for (int i = 0; i < ND; ++i) z[i] = {0.0f, 0.0f};
+#pragma unroll 1
+      for (int st = 0; st <= (euler ? 0 : 3); ++st) {
+        for (int i = 0; i < ND; ++i) {
+          const Dual si = s[i];
+          if (st == 0) {
+            tmp[i] = si;
+          } else {
+            const Dual ki = kx[i], zi = z[i];
+            tmp[i] = Dual{mtgp_rk4_in(st, si.v, ki.v, zi.v, dt), mtgp_rk4_in(st, si.d, ki.d, zi.d, dt)};
+            if (st == 1 || st == 2) z[i] = Dual{mtgp_rk4_zero(st, zi.v, ki.v), mtgp_rk4_zero(st, zi.d, ki.d)};
+          }
+        }
+        rhs(st == 0 ? t : mtgp_rk4_time(st, t, dt), tmp, kx);
+        for (int i = 0; i < ND; ++i) {
+          const Dual ki = kx[i];
+          if (st == 0) {
+            f0[i] = ki;
+            acc[i] = {mtgp_rk4_acc(0, 0.0f, ki.v), mtgp_rk4_acc(0, 0.0f, ki.d)};
+          } else {
+            const Dual ai = acc[i];
+            acc[i] = {mtgp_rk4_acc(st, ai.v, ki.v), mtgp_rk4_acc(st, ai.d, ki.d)};
+          }
+        }
+      }
+      for (int i = 0; i < ND; ++i) {
+        const Dual si = s[i], fi = f0[i], ai = acc[i];
+        y1[i] = euler ? Dual{si.v + fi.v * dt, si.d + fi.d * dt}
+                      : Dual{mtgp_rk4_out(si.v, ai.v, dt), mtgp_rk4_out(si.d, ai.d, dt)};
+      }
+      while (ks < S && ts[ks] <= tn) {  // SaveAt(ts) by the dense output
+        const float thq = mtgp_cs_rescale(t, ts[ks], tn);
+        for (int i = 0; i < ND; ++i) {
+          const Dual si = s[i], yi = y1[i], fi = f0[i], ki = kx[i];
+          tmp[i] = euler ? Dual{mtgp_cs_linear(si.v, yi.v, thq), mtgp_cs_linear(si.d, yi.d, thq)}
+                         : Dual{mtgp_cs_hermite(si.v, yi.v, fi.v * dt, ki.v * dt, thq),
+                                mtgp_cs_hermite(si.d, yi.d, fi.d * dt, ki.d * dt, thq)};
+        }
+        save_point(ks, tmp);
+        ++ks;
+      }
+      for (int i = 0; i < ND; ++i) s[i] = y1[i];
+      ++steps;
+      t = tn;
+      tn = mtgp_cs_next_end(t, h, t_end);
+      const bool ok = !bad(s);
+      if (prev_ok && !ok) break;  // Event(cond_fn_nan), dyn.py:94
+      prev_ok = ok;
+    }
+    q_saved = ks - 1;
+  }
+  // the +inf fill after the event (constants), as in k_ctl_grad
+  float F, dF;
+  if constexpr (ENV == 0) {
+    if (kof) {
+      for (int i = 0; i < ND; ++i) fill[i] = {kInf, 0.0f};
+      for (int q = q_saved + 1; q < S; ++q) {
+        const int need = settled ? (a_set ? -1 : Kt - 1) : kof[0] - 1;
+        if (q > need) break;
+        save_point(q, fill);
+      }
+      if (!settled) {  // no success: first_success = argmax of all-false = 0
+        fs = 0;
+        Kt = kof[0];
+        settled = true;
+        prefix_done();
+      }
+      cs = Kt < S ? mtgp_dl_add(AK, mtgp_dl(0.0f, 0.0f)) : AK;
+      const MtgpDual Fd = mtgp_dl_cadd((float)(fs + (fs == 0) * S), cs);
+      out[0] = Fd.v;
+      out[1] = Fd.d;
+      return;
+    }
+    if (q_saved + 1 < S && settled) cs = mtgp_dl_add(cs, mtgp_dl(0.0f, 0.0f));
+    if (!settled) {
+      fs = 0;
+      cs = S > 1 ? mtgp_dl_add(c0, mtgp_dl(0.0f, 0.0f)) : c0;
+    }
+    const MtgpDual Fd = mtgp_dl_cadd((float)(fs + (fs == 0) * S), cs);
+    F = Fd.v;
+    dF = Fd.d;
+  } else {
+    F = q_saved + 1 < S ? mtgp_qnan() : cs.v;
+    dF = cs.d;
+  }
+  out[0] = F;
+  out[1] = dF;
+}
+
 // ---- dual-number program code (mtgp_jit_dual.h): count, scan, subroutines, emit --------------
 // Units: one per (individual p, program j), each starting on a 64-byte line; the shared
 // subroutines (sin, cos, exp, log, tanh, sqrt) at the start of the buffer.  All on the stream, no
@@ -1344,6 +1780,29 @@ static bool grad_args(GradArgs& A, const MtgpModel* model, const MtgpInstr* prog
   return true;
 }
 
+// Launch k_ctl_grad_wide<ENV, DP> with the dynamic LDS of the actual state and data sizes.  Both
+// forms can pass the 64 KB a kernel gets by default, so each instantiation raises its limit to its
+// ceiling (ND = 20, D = kWideData) once per device, not per launch.
+template <int ENV, bool DP>
+static int wide_launch(const GradArgs& A, dim3 grid, int nd, int D, hipStream_t s) {
+  constexpr size_t kSlotBytes = sizeof(Dual) * kWideBlock;
+  constexpr int kMaxBytes = (int)(wide_slots(DP, 4 + kWideState, kWideData) * kSlotBytes);
+  static_assert(kMaxBytes <= 160 * 1024, "one wave's columns fit the LDS of a CU");
+  static std::atomic<uint64_t> raised{0};  // bit d: device d's limit is set
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) return MTGP_ERR_LAUNCH;
+  if (dev < 0 || dev >= 64 || !((raised.load(std::memory_order_acquire) >> dev) & 1u)) {
+    if (hipFuncSetAttribute((const void*)k_ctl_grad_wide<ENV, DP>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                            kMaxBytes) != hipSuccess)
+      return MTGP_ERR_LAUNCH;
+    if (dev >= 0 && dev < 64) raised.fetch_or(uint64_t(1) << dev, std::memory_order_release);
+  }
+  const size_t bytes = (size_t)wide_slots(DP, nd, D) * kSlotBytes;
+  hipLaunchKernelGGL((k_ctl_grad_wide<ENV, DP>), grid, dim3(kWideBlock), bytes, s, A);
+  if (hipGetLastError() != hipSuccess) return MTGP_ERR_LAUNCH;
+  return MTGP_OK;
+}
+
 extern "C" int mtgp_ctl_grad_jit(const MtgpModel* model, const MtgpInstr* prog, int32_t n_prog, int32_t L,
                                  int32_t P, const float* theta, const int32_t* nparam, int32_t K,
                                  const MtgpRollouts* ro, float* scratch, float* loss_out, float* grad_out,
@@ -1365,7 +1824,10 @@ extern "C" int mtgp_ctl_grad_jit(const MtgpModel* model, const MtgpInstr* prog, 
     return MTGP_ERR_ARG;
   const int na = dyn ? model->state_size : 0;
   const int D = model->n_obs + (dyn ? na + 1 : 0) + model->n_targets;
-  if (na < 0 || na > 3 || D > kCtlData || D + K > MTGP_MAX_DATA) return MTGP_ERR_ARG;
+  if (na < 0 || na > kWideState || D > kWideData || D + K > MTGP_MAX_DATA) return MTGP_ERR_ARG;
+  // register kernels (state_size <= 3, data vector <= kCtlData) or the LDS-column kernel
+  const bool wide = na > 3 || D > kCtlData;
+  if (wide && !dyn) return MTGP_ERR_ARG;  // the static model has the register form only
   if (dyn && (model->prog_state < 0 || model->prog_state + na > n_prog || model->prog_readout_save < 0 ||
               model->prog_readout_save >= n_prog))
     return MTGP_ERR_ARG;
@@ -1375,11 +1837,25 @@ extern "C" int mtgp_ctl_grad_jit(const MtgpModel* model, const MtgpInstr* prog, 
   // the general Acrobot mask keeps its cost prefixes behind the partials (mtgp.h: scratch size)
   if (ro->fit_kof) A.hist = scratch + (size_t)P * K * ro->R * 2;
   hipStream_t s = (hipStream_t)stream;
-  const int jrc = dual_jit_prepare(A, jit, D, s);
+  // (the dual-number code is a register-data design: wide states interpret, whatever `jit` holds)
+  const int jrc = dual_jit_prepare(A, wide ? nullptr : jit, D, s);
   if (jrc != MTGP_OK) return jrc;
   const long lanes = (long)P * grad_lanes_per(K, ro->R);  // whole waves per individual (grad_lane)
+  if (wide) {
+    const int nd = nv + na;
+    const dim3 wgrid((unsigned)(lanes / kWideBlock));
+    int rc;
+    if (model->env == MTGP_ENV_ACROBOT) rc = dopri5 ? wide_launch<0, true>(A, wgrid, nd, D, s) : wide_launch<0, false>(A, wgrid, nd, D, s);
+    else if (model->env == MTGP_ENV_HARMONIC_OSCILLATOR)
+      rc = dopri5 ? wide_launch<1, true>(A, wgrid, nd, D, s) : wide_launch<1, false>(A, wgrid, nd, D, s);
+    else rc = dopri5 ? wide_launch<2, true>(A, wgrid, nd, D, s) : wide_launch<2, false>(A, wgrid, nd, D, s);
+    if (rc != MTGP_OK) return rc;
+    hipLaunchKernelGGL(k_grad_reduce, dim3((unsigned)(((long)P * K + 255) / 256)), dim3(256), 0, s, A);
+    if (hipGetLastError() != hipSuccess) return MTGP_ERR_LAUNCH;
+    return MTGP_OK;
+  }
   const dim3 grid((unsigned)((lanes + 255) / 256)), block(256);
-#define MTGP_CG2(E, DPV)                                                                  \
+#define MTGP_CG2(E, DPV)                                                                 \
   switch (na) {                                                                           \
     case 0: hipLaunchKernelGGL((k_ctl_grad<E, 0, DPV>), grid, block, 0, s, A); break;     \
     case 1: hipLaunchKernelGGL((k_ctl_grad<E, 1, DPV>), grid, block, 0, s, A); break;     \
