@@ -23,6 +23,13 @@
 #ifndef MTGP_FLAT_LANES
 #define MTGP_FLAT_LANES 16  // lanes per program of the lane-per-program flattener (A/B kernel)
 #endif
+// Fixed-step stage loops (round 7, DESIGN.md "Round 7"); 0 = the round-6 form of each:
+#ifndef MTGP_DEAD_ZERO
+#define MTGP_DEAD_ZERO 1    // a lane whose solve has ended (or an inactive one) carries the state +0, not the
+#endif                      // non-finite state that ended it, so its wave keeps to the fast paths
+#ifndef MTGP_FAIR_DPP
+#define MTGP_FAIR_DPP 1     // FairShare's 16-lane minimum by DPP row operations (1) or LDS shuffles (0)
+#endif
 
 // ---- diagnostics (0 = shipped)
 #ifndef MTGP_AB_NOPROG
@@ -34,6 +41,9 @@
 #ifndef MTGP_AB_FBCOUNT
 #define MTGP_AB_FBCOUNT 0     // count JIT calls that report slow sin/cos lanes (mtgp_ab_fb_count)
 #endif
+#ifndef MTGP_AB_PATHCOUNT
+#define MTGP_AB_PATHCOUNT 0   // count the dynamic JIT loop's wave-stages that leave a fast path, split by
+#endif                        // whether a live lane needed it (mtgp_ab_path_count, scripts/path_count.py)
 #ifndef MTGP_AB_NOINTERP
 #define MTGP_AB_NOINTERP 0    // JIT kernels without the interpreter (with NOFALLBACK: a readable ISA of the hot loop)
 #endif

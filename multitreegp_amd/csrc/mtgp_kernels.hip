@@ -167,6 +167,18 @@ __device__ __forceinline__ AcroConst acro_const(float l1, float l2, float m1, fl
 // gives NaN either way.  The reciprocal part depends on d alone, so the three divisions of the
 // Acrobot drift by d1 share one (two v_rcp instead of four, and no scale/fixup).  Callers test the
 // range with one wave-uniform branch and fall back to `/` otherwise.
+#if MTGP_AB_PATHCOUNT  // diagnostic: the dynamic JIT loop's wave-stages that leave a fast path, by who needed it
+// [2 * path + who]: path 0 the general branch of ctl_obs_apply, 1 the slow branch of mtgp_fmod_2pi
+// (per wrap), 2 the drift's slow trig reduction, 3 / 4 its div_safe fallbacks (num, n1); who 0 =
+// some live lane needed it, 1 = only ended / inactive lanes did.  [10] wave-stages, [11] those of
+// a wave that holds an ended or inactive lane.  pc: 0 = not counted, 1 = a live lane, 2 = an ended one.
+__device__ unsigned long long g_ab_path_count[12];
+__device__ __forceinline__ void path_count(int path, bool need, int pc) {
+  if (uni(pc) == 0) return;  // (pc is 0 in every lane or in none: a call site's constant)
+  const uint64_t any = __builtin_amdgcn_ballot_w64(need), live = __builtin_amdgcn_ballot_w64(need && pc == 1);
+  if (any != 0 && (threadIdx.x & 63) == 0) atomicAdd(&g_ab_path_count[2 * path + (live != 0 ? 0 : 1)], 1ull);
+}
+#endif
 __device__ __forceinline__ float div_rcp(float d) {
   const float r = __builtin_amdgcn_rcpf(d);
   return __builtin_fmaf(__builtin_fmaf(-d, r, 1.0f), r, r);
@@ -215,7 +227,8 @@ __device__ __forceinline__ bool trig_args_small(float v) {
 }
 
 __device__ __forceinline__ void acro_drift(const AcroConst& k, const float x[4], float u_raw,
-                                           float dx[4], bool fastdiv = false) {
+                                           float dx[4], bool fastdiv = false, int pc = 0) {
+  (void)pc;  // (MTGP_AB_PATHCOUNT only)
   const float control = mtgp_clip1(u_raw);
   const float th1 = x[0], th2 = x[1], thd1 = x[2], thd2 = x[3];
 #if MTGP_AB_NODRIFT  // diagnostic (mtgp_ab.h): no drift arithmetic at all
@@ -233,6 +246,9 @@ __device__ __forceinline__ void acro_drift(const AcroConst& k, const float x[4],
   float s1 = mtgp_trig_pi_fast(th1, 0, &f2);
   float ca = mtgp_trig_pi_fast(ea, 1, &f3), cb = mtgp_trig_pi_fast(eb, 1, &f4);
   (void)f0; (void)f1; (void)f2; (void)f3; (void)f4;
+#if MTGP_AB_PATHCOUNT
+  path_count(2, !(trig_args_small(th1) && trig_args_small(th2)), pc);
+#endif
   if (__builtin_expect(!wave_all(trig_args_small(th1) && trig_args_small(th2)), 0)) {
     s2 = mtgp_sinf(th2);
     c2 = mtgp_cosf(th2);
@@ -260,6 +276,10 @@ __device__ __forceinline__ void acro_drift(const AcroConst& k, const float x[4],
     if (__builtin_expect(wave_all(div_safe(num)), 1)) a2 = div_by(num, den, div_rcp(den));
     else a2 = num / den;
     const float n1 = -((d2 * a2) + phi1);
+#if MTGP_AB_PATHCOUNT
+    path_count(3, !div_safe(num), pc);
+    path_count(4, !div_safe(n1), pc);
+#endif
     if (__builtin_expect(wave_all(div_safe(n1)), 1)) a1 = div_by(n1, d1, r1);
     else a1 = n1 / d1;
     dx[0] = thd1;
@@ -365,8 +385,10 @@ __device__ __forceinline__ void obs_noise_vec(const ObsNoise<NO>& z, float t, fl
 // nz = +0 a -0 becomes +0 either way), NaN otherwise (0*inf), then the environment's own
 // observation transform (Acrobot: angle wrap, acrobot.py:29-32).
 template <class Env>
-__device__ __forceinline__ void ctl_obs_apply(const float x[Env::NV], const float nz[Env::NV], float y[Env::NV]) {
+__device__ __forceinline__ void ctl_obs_apply(const float x[Env::NV], const float nz[Env::NV], float y[Env::NV],
+                                              int pc = 0) {
   constexpr int NV = Env::NV;
+  (void)pc;  // (MTGP_AB_PATHCOUNT only)
 #if MTGP_AB_NOOBS  // diagnostic: observation = state
 #pragma unroll
   for (int i = 0; i < NV; ++i) y[i] = x[i] + nz[i];
@@ -378,6 +400,25 @@ __device__ __forceinline__ void ctl_obs_apply(const float x[Env::NV], const floa
     fin[j] = mtgp_isfinite(x[j]);
     all = all && fin[j];
   }
+#if MTGP_AB_PATHCOUNT
+  path_count(0, !all, pc);
+  if constexpr (NV == 4) {  // (Acrobot) the two angle wraps: mtgp_fmod_2pi(v + pi) is slow unless |v + pi| < 2^20
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      bool ok = true;
+#pragma unroll
+      for (int j = 0; j < NV; ++j)
+        if (j != i) ok = ok && fin[j];
+      const float v = (ok ? x[i] + nz[i] : mtgp_qnan()) + MTGP_PI_F;
+      path_count(1, !(__builtin_fabsf(v) < 1048576.0f), pc);
+    }
+  }
+  const bool pc_any_dead = __builtin_amdgcn_ballot_w64(pc == 2) != 0;
+  if (uni(pc) != 0 && (threadIdx.x & 63) == 0) {
+    atomicAdd(&g_ab_path_count[10], 1ull);
+    if (pc_any_dead) atomicAdd(&g_ab_path_count[11], 1ull);
+  }
+#endif
   if (__builtin_expect(wave_all(all), 1)) {  // every lane's state finite (the common case): no NaN masking
 #pragma unroll
     for (int i = 0; i < NV; ++i) y[i] = x[i] + nz[i];
@@ -581,8 +622,8 @@ struct EnvAcrobot {
     m2 = ro.params[4 * rr + 3];
     fastdiv = wave_all(acro_div_ok(acro_const(l1, l2, m1, m2)));
   }
-  __device__ __forceinline__ void drift(const float x[4], float u, float dx[4]) const {
-    acro_drift(acro_const(l1, l2, m1, m2), x, u, dx, fastdiv);
+  __device__ __forceinline__ void drift(const float x[4], float u, float dx[4], int pc = 0) const {
+    acro_drift(acro_const(l1, l2, m1, m2), x, u, dx, fastdiv, pc);
   }
   __device__ __forceinline__ static void obs_transform(float y[4]) {
     y[0] = mtgp_wrap_angle(y[0]);
@@ -890,6 +931,18 @@ struct CsClock {
   // save point k is taken in this step (ts[k] <= tn; k < S checked by the caller)
   __device__ __forceinline__ bool saves(const float* ts, int k) const { return uni((int)(ldc(ts, k) <= tn)) != 0; }
 };
+
+// A lane whose solve has ended (or an inactive lane) keeps running the stages with its wave, and
+// every wave-uniform fast-path guard -- the observation's finite test, the wrap's and the drift's
+// range tests -- fails for all 64 lanes while one lane holds the non-finite state that ended it.
+// Nothing reads that state again: the lane's save points are the +inf fill (cs_dense), its event
+// test and state update are switched off, its fitness is settled.  So it carries +0 instead
+// (MTGP_DEAD_ZERO); the stage arithmetic of such a lane is discarded either way.
+template <int N>
+__device__ __forceinline__ void dead_state_clear(float (&s)[N]) {
+#pragma unroll
+  for (int i = 0; i < N; ++i) s[i] = 0.0f;
+}
 
 // RK4 stage input (stage 0: s itself; stages 1..3: s + (sum_j a_ij f_j) dt over the padded tableau
 // row, zero entries multiplied: mtgp_cstep.h) from f = the previous stage's derivative and acc = the
@@ -1285,6 +1338,13 @@ __device__ __forceinline__ ChainOut jit_call_chain_nf(uint64_t addr_, const floa
 // stores, which drop the line from L2 -- sent every post and every read to memory: 105 MB of
 // FETCH and 25 MB of WRITE per C3 launch (profiles/r06/v1_pmc_fair{0,3}_*.json).
 static __device__ uint64_t g_fair[8 * 8 * 2 * 16 * 4 * 16];
+// min(m, m of the lane that DPP control CTRL names within the row); a source lane that is switched
+// off leaves m (old = INT_MAX, the identity of min)
+template <int CTRL>
+__device__ __forceinline__ int row_min_dpp(int m) {
+  const int o = __builtin_amdgcn_update_dpp(0x7fffffff, m, CTRL, 0xf, 0xf, false);
+  return o < m ? o : m;
+}
 struct FairShare {
   uint64_t* tab;
   uint64_t seen;
@@ -1307,11 +1367,20 @@ struct FairShare {
   __device__ __forceinline__ void step(int lane, uint32_t st) {
     const bool valid = lane < 16 && (uint32_t)(seen >> 32) == tag && (uint32_t)lane != slot;
     int m = valid ? (int)(uint32_t)seen : 0x7fffffff;
+#if MTGP_FAIR_DPP
+    // the 16 posts sit in one DPP row: xor 1 and xor 2 as quad permutes, then rotates by 4 and 8 (min
+    // is symmetric) -- four VALU operations and no LDS round trip (a shuffle is a ds_bpermute and its wait)
+    m = row_min_dpp<0xB1>(m);   // quad_perm:[1,0,3,2]
+    m = row_min_dpp<0x4E>(m);   // quad_perm:[2,3,0,1]
+    m = row_min_dpp<0x124>(m);  // row_ror:4
+    m = row_min_dpp<0x128>(m);  // row_ror:8
+#else
 #pragma unroll
     for (int w = 1; w < 16; w <<= 1) {
       const int o = __shfl_xor(m, w, kWave);
       m = o < m ? o : m;
     }
+#endif
     const int mn = __builtin_amdgcn_readfirstlane(m);
     const int lv = mn == 0x7fffffff ? 2 : ((int)st > mn + margin ? 0 : ((mode == 1 && (int)st <= mn) ? 3 : 2));
     if (lv != level) {  // (s_setprio takes an immediate)
@@ -1420,6 +1489,10 @@ __device__ __forceinline__ void ctl_dynamic_jit(const KArgs& A, const Lane& Ln) 
   CsClock clk;
   clk.init(A);
   int k = 0;  // next save point
+  if (MTGP_DEAD_ZERO && dead) {  // an inactive lane: as a lane whose solve has ended
+    dead_state_clear<NV>(x);
+    dead_state_clear<NA>(a);
+  }
   const bool fair_on = uni(A.fair) != 0;
   FairShare fair;
   if (fair_on) fair.init(A);
@@ -1447,12 +1520,20 @@ __device__ __forceinline__ void ctl_dynamic_jit(const KArgs& A, const Lane& Ln) 
       }
       // one call: the readout (y, u folded: reads [0, a, 0, tar]) returns u in v26, and the state
       // programs it falls into read their u slot from there ([y, a, u, tar]) -- MtgpJitChain.put
+#if MTGP_AB_PATHCOUNT
+      ctl_obs_apply<Env>(xt, nzv, y, dead ? 2 : 1);
+#else
       ctl_obs_apply<Env>(xt, nzv, y);
+#endif
 #pragma unroll
       for (int i = 0; i < NV; ++i) dv[i] = y[i];
       const ChainOut c = jit_call_chain_nf(u_readout, dv, 0);
 #pragma unroll
       for (int j = 0; j < NA; ++j) ka[j] = c.v[1 + j < mtgp::kJitChainMax ? 1 + j : 0];
+#if MTGP_AB_PATHCOUNT
+      if constexpr (std::is_same<Env, EnvAcrobot>::value) env.drift(xt, c.v[0], kx, dead ? 2 : 1);
+      else
+#endif
       env.drift(xt, c.v[0], kx);
       if (ST == 0) {
 #pragma unroll
@@ -1504,6 +1585,10 @@ __device__ __forceinline__ void ctl_dynamic_jit(const KArgs& A, const Lane& Ln) 
     if (ev) {  // the solve ends: later save points are the +inf fill
       dead = true;
       if (k < S) Env::fit_kill(fit);
+      if (MTGP_DEAD_ZERO) {  // nothing reads this lane's state again (dead_state_clear)
+        dead_state_clear<NV>(x);
+        dead_state_clear<NA>(a);
+      }
     }
     clk.advance();
     if (!TRAJ && wave_all(fit.settled || dead)) break;
@@ -1660,6 +1745,10 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((NA > 
   CsClock clk;
   clk.init(A);
   int k = 0;  // next save point
+  if (MTGP_DEAD_ZERO && dead) {  // an inactive lane: as a lane whose solve has ended
+    dead_state_clear<NV>(x);
+    dead_state_clear<NA>(a);
+  }
   while (clk.live()) {
     const float t = clk.t, dt = clk.dt();
     // (the stage input reads the b-weighted sum before f_{stage-1}'s term -- mtgp_rk4_in_acc, the
@@ -1731,6 +1820,10 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((NA > 
     if (ev) {
       dead = true;
       if (k < S) Env::fit_kill(fit);  // save points of the +inf fill follow
+      if (MTGP_DEAD_ZERO) {            // nothing reads this lane's state again (dead_state_clear)
+        dead_state_clear<NV>(x);
+        dead_state_clear<NA>(a);
+      }
     }
     clk.advance();
     if (!TRAJ && wave_all(fit.settled || dead)) break;
@@ -1817,6 +1910,7 @@ __device__ __forceinline__ void ctl_static_jit(const KArgs& A, const Lane& Ln) {
   CsClock clk;
   clk.init(A);
   int k = 0;
+  if (MTGP_DEAD_ZERO && dead) dead_state_clear<NV>(x);  // an inactive lane: as a lane whose solve has ended
   const bool fair_on = uni(A.fair) != 0;
   FairShare fair;
   if (fair_on) fair.init(A);
@@ -1880,6 +1974,7 @@ __device__ __forceinline__ void ctl_static_jit(const KArgs& A, const Lane& Ln) {
     if (ev) {
       dead = true;
       if (k < S) Env::fit_kill(fit);
+      if (MTGP_DEAD_ZERO) dead_state_clear<NV>(x);
     }
     clk.advance();
     if (!TRAJ && wave_all(fit.settled || dead)) break;
@@ -1974,6 +2069,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) k
   CsClock clk;
   clk.init(A);
   int k = 0;
+  if (MTGP_DEAD_ZERO && dead) dead_state_clear<NV>(x);  // an inactive lane: as a lane whose solve has ended
   while (clk.live()) {
     const float t = clk.t, dt = clk.dt();
     // (the stage input reads the b-weighted sum before f_{stage-1}'s term -- mtgp_rk4_in_acc, the
@@ -2020,6 +2116,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) k
     if (ev) {
       dead = true;
       if (k < S) Env::fit_kill(fit);
+      if (MTGP_DEAD_ZERO) dead_state_clear<NV>(x);
     }
     clk.advance();
     if (!TRAJ && wave_all(fit.settled || dead)) break;
@@ -5100,6 +5197,13 @@ extern "C" int mtgp_ab_wave_times(unsigned long long* t, unsigned int* hw, int n
   if (hipMemcpyFromSymbol(t, HIP_SYMBOL(g_wave_time), (size_t)n * 2 * sizeof(unsigned long long)) != hipSuccess) return -1;
   if (hipMemcpyFromSymbol(hw, HIP_SYMBOL(g_wave_hw), (size_t)n * 2 * sizeof(unsigned int)) != hipSuccess) return -1;
   return n;
+}
+#endif
+#if MTGP_TU_ACRO && MTGP_AB_PATHCOUNT
+extern "C" int mtgp_ab_path_count(unsigned long long* host) {  // diagnostic build only; reads and clears
+  if (hipMemcpyFromSymbol(host, HIP_SYMBOL(g_ab_path_count), 12 * sizeof(unsigned long long)) != hipSuccess) return -1;
+  const unsigned long long z[12] = {0};
+  return hipMemcpyToSymbol(HIP_SYMBOL(g_ab_path_count), z, sizeof(z)) == hipSuccess ? 0 : -1;
 }
 #endif
 #if MTGP_TU_ACRO && MTGP_AB_FBCOUNT

@@ -27,6 +27,8 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--config", default="c3", choices=["c3"])
 ap.add_argument("--no-schedule", action="store_true")
 ap.add_argument("--save", default="", help="write the raw per-wave data (.npz)")
+ap.add_argument("--dead", action="store_true", help="also print the wave durations split by whether the wave holds "
+                                                    "a lane whose solve ends (its last save point is the +inf fill)")
 a = ap.parse_args()
 assert nat.LIB_PATH.endswith("libmtgp_hip_wt.so"), "run with MTGP_LIB=<the MTGP_AB_WAVETIME build>"
 args = bench.apply_config_defaults(argparse.Namespace(pop=None, rollouts=None, ode_steps=200, config=a.config,
@@ -73,6 +75,23 @@ out = {"waves": int(live.sum()), "simds": int(len(simds)), "waves_per_simd": [in
        "simd_busy_rel_mean": float(busy.mean() / span), "simd_busy_rel_p10": float(np.percentile(busy, 10) / span),
        "start_spread_rel": float((start.max() - start.min()) / span), "schedule": not a.no_schedule}
 print(json.dumps(out))
+if a.dead:  # (every wave of the C3 launch is live, so row w of T is wave w of the grid)
+    res = eng.evaluate(pd, data, trajectories=True, check=False, schedule=not a.no_schedule)
+    torch.cuda.synchronize()
+    fl = res["_flat"]
+    P, R = pop.shape[0], args.rollouts
+    fill = torch.isinf(res["xs"]).all(dim=1).reshape(-1, P, R)  # [S, P, R]: save point of the +inf fill
+    share = fill.float().mean(dim=(0, 2)).cpu().numpy()        # per individual: share of its lane-saves after the end
+    order = fl.order.cpu().numpy() if fl.order is not None else np.arange(P)
+    G = 64 // (1 << max(R - 1, 0).bit_length())
+    assert len(dur) * G == P, "a wave count other than P / G: rows of T are not grid waves"
+    wshare = share[order].reshape(-1, G).mean(axis=1)           # per wave: share of lane-steps that are dead
+    grp = {"no_dead_lane": wshare == 0, "dead_lane": wshare > 0, "dead_share_over_25pct": wshare > 0.25}
+    print(json.dumps({"dead_split": {k: {"waves": int(m.sum()), "dur_rel_mean": float(dur[m].mean() / dur.mean()) if m.any() else None,
+                                         "dur_rel_p90": float(np.percentile(dur[m], 90) / dur.mean()) if m.any() else None,
+                                         "dead_share_mean": float(wshare[m].mean()) if m.any() else None}
+                                     for k, m in grp.items()},
+                      "corr_dur_dead_share": float(np.corrcoef(dur, wshare)[0, 1])}))
 if a.save:  # raw per-wave data + the schedule's inputs, for offline analysis
     res = eng.evaluate(pd, data, trajectories=True, check=False, schedule=not a.no_schedule)
     torch.cuda.synchronize()
