@@ -26,11 +26,13 @@
 
 #include <stdint.h>
 
+#include "mtgp_host.h" /* MtgpEvolveConfig (the device evolve entry points, ABI v22) */
+
 #ifdef __cplusplus
 extern "C" {
 #endif
 
-#define MTGP_ABI_VERSION 21
+#define MTGP_ABI_VERSION 22
 
 /* ---------------------------------------------------------------- limits */
 #define MTGP_MAX_FUNCS 128   /* node functions 2 + K + V (gp.py:135-199)       */
@@ -495,6 +497,43 @@ int mtgp_sr_grad_jit(const MtgpModel* model, const MtgpInstr* prog, int32_t n_pr
  * words written (out == NULL: counted), or < 0 (untranslatable / out too short) */
 int mtgp_jit_dual_translate_host(const MtgpInstr* prog, int32_t L, int32_t D, const float* theta, int32_t K,
                                  uint32_t base, uint32_t* out, int32_t max_words);
+
+/* ------------------------------------------------------- device evolve (ABI v22)
+ * The evolution step of mtgp_host.h (mtgp_evolve_populations / mtgp_sample_population) on the
+ * device, draw for draw: columns f, a, b of every row equal the host library's bit for bit, and so
+ * do the values except where the device's f64 log rounds differently inside the normal draw (at
+ * most 1 float32 ulp).  Limits: N <= MTGP_MAX_NODES, n_funcs <= MTGP_MAX_FUNCS, tournament_size <=
+ * MTGP_EVOLVE_MAX_TOURNAMENT, slots in 0..2, every reproduction_prob > 0; population and output base
+ * pointers 16-B aligned.
+ * Anything else returns MTGP_ERR_ARG before any device call.
+ *
+ * The small tables of `cfg` (slots, op_index, op_prob, var_mask, tournament / type / reproduction
+ * probabilities) are packed once into a blob the caller uploads (16-B aligned device memory);
+ * later calls pass the same `cfg` (host memory: scalars and checks) with that blob. */
+#define MTGP_EVOLVE_MAX_TOURNAMENT 64
+/* bytes of the blob; packed into `blob` (host memory, `capacity` bytes) when blob != NULL */
+int mtgp_evolve_config_pack(const MtgpEvolveConfig* cfg, int32_t num_pop, int32_t num_trees, void* blob,
+                            int32_t capacity);
+/* bytes of mtgp_evolve_device's workspace (the two fitness orders per population) */
+int mtgp_evolve_workspace_bytes(int32_t num_pop, int32_t pop_size);
+/* One generation on `stream`: rank kernel, elite gather, one wave per (population, pair); no host
+ * synchronisation, no device-to-host copy.  populations [num_pop, pop_size, num_trees, N, 4],
+ * fitness [num_pop, pop_size], workspace and out [num_pop, E + 2 * pairs, num_trees, N, 4] are
+ * device memory; out must not overlap populations.  The migrated population is read through the
+ * order arrays, never materialised.  Returns the output population size or MTGP_ERR_*. */
+int mtgp_evolve_device(const float* populations, const float* fitness, int32_t num_pop, int32_t pop_size,
+                       int32_t num_trees, int32_t N, const MtgpEvolveConfig* cfg, const void* blob, uint64_t seed,
+                       void* workspace, float* out, void* stream);
+/* initialize_population into device memory out [num_pop, pop_size, num_trees, N, 4] */
+int mtgp_sample_population_device(int32_t num_pop, int32_t pop_size, int32_t num_trees, int32_t N,
+                                  const MtgpEvolveConfig* cfg, const void* blob, uint64_t seed, float* out,
+                                  void* stream);
+/* the same code on the CPU (host memory, no GPU needed): the twins the parity tests compare with
+ * the host library bit for bit */
+int mtgp_evolve_device_host(const float* populations, const float* fitness, int32_t num_pop, int32_t pop_size,
+                            int32_t num_trees, int32_t N, const MtgpEvolveConfig* cfg, uint64_t seed, float* out);
+int mtgp_sample_population_device_host(int32_t num_pop, int32_t pop_size, int32_t num_trees, int32_t N,
+                                       const MtgpEvolveConfig* cfg, uint64_t seed, float* out);
 
 /* Wall time of the calling thread's last timed mtgp_eval_rk4 kernel (ms), measured with
  * hipEvents recorded on its stream around the launch; -1 if none.  Synchronises that event.

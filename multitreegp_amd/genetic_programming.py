@@ -131,8 +131,8 @@ class GeneticProgramming:
         self.vmap_foriloop = TreeEvaluator(self.library, max_nodes, device)
         self.device = device
         self.operators = Operators(self.library, max_nodes, max_init_depth, coefficient_sd)
-        if evolve_backend not in ("native", "numpy"):
-            raise ValueError(f"evolve_backend must be 'native' or 'numpy', got {evolve_backend!r}")
+        if evolve_backend not in ("native", "numpy", "device"):
+            raise ValueError(f"evolve_backend must be 'native', 'numpy' or 'device', got {evolve_backend!r}")
         self.evolve_backend = evolve_backend
         self._evolver = None
 
@@ -148,7 +148,12 @@ class GeneticProgramming:
         coefficients (gp.py:418-422; multitreegp_amd.coefficients), split over the ranks like
         shard_optimise (gp.py:264-267) and all-gathered.  Under Dopri5 + PIDController the
         step sizes carry no tangent, as diffrax's controller stops their gradient
-        (multitreegp_amd.coefficients)."""
+        (multitreegp_amd.coefficients).
+
+        The result follows the input: numpy in, numpy out; a CUDA tensor (evolve_backend "device")
+        is evaluated where it lies and fitness and population come back as CUDA tensors."""
+        if isinstance(populations, torch.Tensor) and populations.is_cuda:
+            return self._evaluate_population_device(populations, data)
         pops = np.asarray(populations, dtype=np.float32)
         P = self.num_populations * self.population_size
         flat = pops.reshape(P, *pops.shape[2:])
@@ -177,6 +182,49 @@ class GeneticProgramming:
         return fitness.reshape(self.num_populations, self.population_size), \
             flat.reshape(self.num_populations, self.population_size, *flat.shape[1:])
 
+    def _evaluate_population_device(self, populations: torch.Tensor, data) -> Tuple[torch.Tensor, torch.Tensor]:
+        """evaluate_population of a population on the GPU: no host copy of it is made, the shards
+        are device slices.  The same values as the numpy path: the fitness vector (a few KB) comes
+        to the host for the best-so-far bookkeeping, which copies one candidate back; on an
+        optimising generation the 50 best are gathered to the host, optimised as there and
+        scattered into a copy on the device.  With several ranks every rank holds the whole
+        population and the all-gathered fitness (moved back to the device under gloo)."""
+        dev = populations.device
+        P = self.num_populations * self.population_size
+        flat = populations.to(torch.float32).reshape(P, *populations.shape[2:]).contiguous()
+        g = self.current_generation
+        if self.coefficient_optimisation:
+            CoefficientOptimiser.check_data(self.fitness_function.prepare(data))
+        if self.coefficient_optimisation and g > 10 and (g + 1) % 5 == 0:
+            raw = mdist.sharded_fitness(lambda lo, hi: self._evaluate_shard_device(flat, lo, hi, data, 0.0), P)
+            raw = raw.cpu().numpy()
+            best_idx = np.argsort(raw, kind="stable")[:50]
+            idx_dev = torch.from_numpy(best_idx).to(dev)
+            best = flat[idx_dev].cpu().numpy()
+            opt_fit, opt_pop = mdist.sharded_rows(
+                lambda lo, hi: self._optimise_shard(best[lo:hi], data), len(best_idx), tuple(flat.shape[1:]))
+            flat = flat.clone()
+            flat[idx_dev] = torch.from_numpy(np.ascontiguousarray(opt_pop, np.float32)).to(dev)
+            raw[best_idx] = opt_fit
+            counts = (flat[..., 0] != 0).sum(dim=tuple(range(1, flat.ndim - 1))).cpu().numpy().astype(np.float32)
+            fitness = (raw + np.float32(self.size_parsinomy) * counts).astype(np.float32)
+        else:
+            fitness = mdist.sharded_fitness(lambda lo, hi: self._evaluate_shard_device(flat, lo, hi, data), P)
+            fitness = fitness.cpu().numpy()
+        best = int(np.argmin(fitness))
+        if g < self.num_generations:
+            self.best_solutions[g] = flat[best].cpu().numpy()
+            self.best_fitnesses[g] = fitness[best]
+        return torch.from_numpy(fitness).to(dev).reshape(self.num_populations, self.population_size), \
+            flat.reshape(self.num_populations, self.population_size, *flat.shape[1:])
+
+    def _evaluate_shard_device(self, flat: torch.Tensor, lo: int, hi: int, data, parsimony=None) -> torch.Tensor:
+        """_evaluate_shard of a population that already lies on the GPU: the shard is a slice."""
+        eng = self._engine() if parsimony is None else self.vmap_foriloop.engine(self.fitness_function, parsimony)
+        if hi <= lo:
+            return torch.empty((0,), dtype=torch.float32, device=eng.device)
+        return eng.evaluate(flat[lo:hi].to(eng.device), data)["fitness"]
+
     def _optimise_shard(self, cands: np.ndarray, data):
         """GeneticProgramming.optimise (gp.py:454-473) of this rank's candidates on its GPU."""
         if len(cands) == 0:
@@ -194,8 +242,17 @@ class GeneticProgramming:
         return eng.evaluate(pop_dev, data)["fitness"]
 
     # --------------------------------------------------------------- host side
-    def initialize_population(self, key) -> np.ndarray:
-        """gp.py:298-308 with the numpy sampler (multitreegp_amd.sampling)."""
+    def _device_evolver(self):
+        if self._evolver is None:
+            from .device_evolve import DeviceEvolver
+            self._evolver = DeviceEvolver.for_strategy(self)
+        return self._evolver
+
+    def initialize_population(self, key):
+        """gp.py:298-308 with the numpy sampler (multitreegp_amd.sampling); evolve_backend "device":
+        sampled on the GPU (the stream of mtgp_sample_population), a CUDA tensor."""
+        if self.evolve_backend == "device":
+            return self._device_evolver().sample_population(self.population_size, _seed_of(key))
         return sample_population(_seed_of(key), self.library, self.population_size, self.num_populations,
                                  self.max_init_depth, self.max_nodes, self.coefficient_sd)
 
@@ -204,7 +261,12 @@ class GeneticProgramming:
         selection + crossover / mutation / resampling.  evolve_backend "native" (default): the C++
         host library (multitreegp_amd.host, include/mtgp_host.h) seeded with `key`; "numpy": the
         numpy restatement (multitreegp_amd.genetic_operators) on PCG64 seeded with `key` (a JAX
-        key's words or an int)."""
+        key's words or an int); "device": the HIP kernels (multitreegp_amd.device_evolve), the host
+        library's result draw for draw, CUDA tensors in and out."""
+        if self.evolve_backend == "device":
+            out = self._device_evolver().evolve(populations, fitness, _seed_of(key), self.current_generation)
+            self.current_generation += 1
+            return out
         if self.evolve_backend == "native":
             if self._evolver is None:
                 from .host import HostEvolver
