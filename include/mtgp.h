@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define MTGP_ABI_VERSION 22
+#define MTGP_ABI_VERSION 23
 
 /* ---------------------------------------------------------------- limits */
 #define MTGP_MAX_FUNCS 128   /* node functions 2 + K + V (gp.py:135-199)       */
@@ -534,6 +534,61 @@ int mtgp_evolve_device_host(const float* populations, const float* fitness, int3
                             int32_t num_trees, int32_t N, const MtgpEvolveConfig* cfg, uint64_t seed, float* out);
 int mtgp_sample_population_device_host(int32_t num_pop, int32_t pop_size, int32_t num_trees, int32_t N,
                                        const MtgpEvolveConfig* cfg, uint64_t seed, float* out);
+
+/* ------------------------------------------------------- device optimise (ABI v23)
+ * The host side of coefficient optimisation (multitreegp_amd/coefficients.py: coefficient_rows,
+ * parameterise, Adam.update, the best-epoch choice of optimise) on the device, bit for bit, so the
+ * candidates of an optimising generation never leave the GPU (multitreegp_amd/csrc/mtgp_optim_core.h
+ * holds the rules, mtgp_optim.hip the kernels: one wave per candidate).  Every call runs on
+ * `stream`, synchronises nothing and copies nothing to the host.
+ * cands [B, T, N, 4]: rows [f, a, b, value]; a coefficient row has f == 1.0f exactly; a candidate's
+ * coefficient rows are numbered in row-major (tree, row) order.
+ * Limits: B, T >= 1, 1 <= N <= MTGP_MAX_NODES, K >= 1, lo >= 0, M >= 1, n_data + K <= MTGP_MAX_DATA,
+ * var_start + n_data + K <= MTGP_MAX_FUNCS; cands / pop / out 16-B aligned, every other array 4-B;
+ * anything else, or a null pointer (theta of mtgp_coef_adam_step excepted), returns MTGP_ERR_ARG
+ * before any device call. */
+/* rowidx [B, T*N]: tree * N + row of the j-th coefficient row (-1 beyond the count); count [B] */
+int mtgp_coef_index(const float* cands, int32_t B, int32_t T, int32_t N, int32_t* rowidx, int32_t* count,
+                    void* stream);
+/* coefficients.parameterise for the window [lo, lo + K) of every candidate's coefficient rows, under
+ * the evaluator's library `lib` (host memory) and its data vector of n_data slots: the k-th
+ * coefficient row becomes a variable row var_start + n_data + (k - lo) and its value goes to
+ * theta[b, k - lo]; coefficient rows outside the window stay; operator indices above the library are
+ * clamped to its top index, variable rows past the data vector read slot n_data - 1.
+ * pop [B, T, N, 4] (not cands), theta [B, K] (0 where unused), nparam [B]. */
+int mtgp_coef_parameterise(const float* cands, int32_t B, int32_t T, int32_t N, const MtgpNodeLibrary* lib,
+                           int32_t n_data, int32_t lo, int32_t K, float* pop, float* theta, int32_t* nparam,
+                           void* stream);
+/* the nine float32 scalars of one optimiser step, which the host computes once per epoch (the
+ * device never evaluates a pow): 1 - b1, b1, 1 - b2, b2, 1 - b1^t, 1 - b2^t, eps_root, eps, -lr */
+typedef struct {
+  float a, b, c, d, c1, c2, eps_root, eps, neg_lr;
+} MtgpAdamScalars;
+/* One epoch for the window [lo, lo + K): per candidate, first the best-epoch tracking -- when
+ * loss[b] is below best_loss[b] (strictly; or `first`; or the first NaN, as np.argmin) the
+ * window's current values are copied to best_vals -- then mu = a g + b mu, nu = c g^2 + d nu,
+ * value += neg_lr * (mu / c1) / (sqrt(nu / c2 + eps_root) + eps) in separate correctly rounded
+ * float32 operations, written to the candidates' value column and, when theta != NULL, theta[b, k].
+ * grad [B, K], loss [B]; mu, nu, best_vals [B, M] over all coefficients of a candidate (M >= every
+ * count, M <= T * N), best_loss [B].  first: the call starts from zero moments and an empty best
+ * (no buffer needs initialising).  commit: the epoch's last window, best_loss[b] takes the loss. */
+int mtgp_coef_adam_step(float* cands, int32_t B, int32_t T, int32_t N, const int32_t* rowidx, const int32_t* count,
+                        int32_t lo, int32_t K, int32_t M, const float* grad, const float* loss,
+                        const MtgpAdamScalars* s, int32_t first, int32_t commit, float* mu, float* nu,
+                        float* best_vals, float* best_loss, float* theta, void* stream);
+/* out (not cands) = cands with best_vals in the value column of the coefficient rows */
+int mtgp_coef_scatter(const float* cands, int32_t B, int32_t T, int32_t N, int32_t M, const float* best_vals,
+                      float* out, void* stream);
+/* the same code on the CPU (host memory, no GPU needed) */
+int mtgp_coef_index_host(const float* cands, int32_t B, int32_t T, int32_t N, int32_t* rowidx, int32_t* count);
+int mtgp_coef_parameterise_host(const float* cands, int32_t B, int32_t T, int32_t N, const MtgpNodeLibrary* lib,
+                                int32_t n_data, int32_t lo, int32_t K, float* pop, float* theta, int32_t* nparam);
+int mtgp_coef_adam_step_host(float* cands, int32_t B, int32_t T, int32_t N, const int32_t* rowidx,
+                             const int32_t* count, int32_t lo, int32_t K, int32_t M, const float* grad,
+                             const float* loss, const MtgpAdamScalars* s, int32_t first, int32_t commit, float* mu,
+                             float* nu, float* best_vals, float* best_loss, float* theta);
+int mtgp_coef_scatter_host(const float* cands, int32_t B, int32_t T, int32_t N, int32_t M, const float* best_vals,
+                           float* out);
 
 /* Wall time of the calling thread's last timed mtgp_eval_rk4 kernel (ms), measured with
  * hipEvents recorded on its stream around the launch; -1 if none.  Synchronises that event.

@@ -18,7 +18,10 @@ host turns the rows of one chunk into variable rows that read data slots ``n_dat
 the evaluator's data vector), so the ordinary flattener produces the programs; other rows keep
 their reference meaning.  The optimiser (optax's Adam restated in float32 numpy, ``adam``, or any
 object with optax's init / update) runs on the host with one state per candidate, as the
-reference's ``jax.vmap(self.optimiser.init)`` / ``jax.vmap(self.optimiser.update)`` do.
+reference's ``jax.vmap(self.optimiser.init)`` / ``jax.vmap(self.optimiser.update)`` do.  Given the
+candidates as a CUDA tensor and the built-in ``Adam``, the same loop runs on the device instead
+(``CoefficientOptimiser._optimise_device``, csrc/mtgp_optim.hip: this module's parameterise, Adam
+and best-epoch choice restated in csrc/mtgp_optim_core.h, bit for bit).
 
 Deviation (documented in DESIGN.md): JAX differentiates w.r.t. the whole value column, which
 also reaches entries read through a reference to a LATER row (the "original column" case of
@@ -84,6 +87,15 @@ class Adam:
             u = mu_hat / (np.sqrt(nu_hat + f(self.eps_root)) + f(self.eps))
         return (f(-self.learning_rate) * u).astype(np.float32), AdamState(count, mu, nu)
 
+    def scalars(self, count: int) -> "nat.MtgpAdamScalars":
+        """The float32 scalars of `update` at step `count` (the same numpy expressions), for
+        mtgp_coef_adam_step: the device never evaluates a pow."""
+        f = np.float32
+        with np.errstate(over="ignore", invalid="ignore", divide="ignore"):
+            return nat.MtgpAdamScalars(f(1 - self.b1), f(self.b1), f(1 - self.b2), f(self.b2),
+                                       f(1) - f(self.b1) ** f(count), f(1) - f(self.b2) ** f(count),
+                                       f(self.eps_root), f(self.eps), f(-self.learning_rate))
+
 
 def adam(learning_rate: float = 0.001, b1: float = 0.9, b2: float = 0.999, eps: float = 1e-8,
          eps_root: float = 0.0) -> Adam:
@@ -129,13 +141,26 @@ def parameterise(candidates: np.ndarray, rows: List[np.ndarray], lib, n_data: in
             t, i = r[lo + k]
             theta[b, k] = pop[b, t, i, 3]
             pop[b, t, i, 0] = np.float32(lib.var_start + n_data + k)
+    return pop, theta, counts, K, extended_library(lib, n_data, K)
+
+
+def extended_library(lib, n_data: int, K: int):
+    """The evaluator's node library followed by K parameter slots (variable rows reading data
+    slots n_data .. n_data + K - 1) as an MtgpNodeLibrary."""
     n_funcs = max(lib.n_funcs, lib.var_start + n_data + K)
     if n_funcs > nat.MAX_FUNCS:
         raise ValueError(f"{n_funcs} node functions with {K} parameters > {nat.MAX_FUNCS}")
     fn = np.zeros(n_funcs, np.int8)
     fn[: lib.n_funcs] = lib.fn_codes
     fn[lib.var_start: n_funcs] = nat.FN_VAR
-    return pop, theta, counts, K, nat.node_library_struct(n_funcs, lib.var_start, fn)
+    return nat.node_library_struct(n_funcs, lib.var_start, fn)
+
+
+def chunk_windows(counts, cap: int) -> List[Tuple[int, int]]:
+    """(lo, K) of every chunk of at most `cap` coefficient rows per candidate, as loss_and_grad
+    walks them: K = the most rows any candidate has in [lo, lo + cap), at least 1."""
+    n_max = max([int(c) for c in counts] + [0])
+    return [(lo, max([1] + [min(lo + cap, int(c)) - lo for c in counts])) for lo in range(0, max(n_max, 1), cap)]
 
 
 # ----------------------------------------------------------------------- the loop
@@ -187,80 +212,47 @@ class CoefficientOptimiser:
         cands = np.ascontiguousarray(candidates, np.float32)
         B, T, N, _ = cands.shape
         rows = coefficient_rows(cands) if rows is None else rows
-        d = eng.prepare_data(data)
-        self.check_data(d)
-        n_data = eng.ff.n_data()
-        specs, _ = eng._specs()
-        cap = self.param_cap(n_data)
+        g = _GradContext(self, data, N)
+        dev = g.dev
         n_max = max([len(r) for r in rows] + [0])
         grads = [np.zeros(len(r), np.float32) for r in rows]
         loss = None
-        dev = eng.device
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        m = eng.model_struct(d)
-        ro = eng.rollouts_struct(d)
-        R = d["R"]
-        L = eng.program_stride(N)
-        grad_fn = self._grad_fn()
-        for lo in range(0, max(n_max, 1), cap):
-            pop, theta, nparam, K, libs = parameterise(cands, rows, eng.lib, n_data, lo, lo + cap)
-            spec_arr = (nat.MtgpProgramSpec * len(specs))()
-            for i, sp in enumerate(specs):  # the reference's data vector + K parameter slots (no slot gap)
-                spec_arr[i].tree, spec_arr[i].n_data, spec_arr[i].zero_mask = sp[0], sp[1] + K, sp[2]
-            spec_dev = torch.frombuffer(bytearray(bytes(spec_arr)), dtype=torch.uint8).to(dev)
-            n_prog = len(specs)
+        for lo in range(0, max(n_max, 1), g.cap):
+            pop, theta, nparam, K, libs = parameterise(cands, rows, eng.lib, g.n_data, lo, lo + g.cap)
             pop_dev = torch.from_numpy(pop).to(dev)
-            prog = torch.empty((B * n_prog * L * 2 + 8,), dtype=torch.int32, device=dev)
-            plen = torch.empty((B, n_prog), dtype=torch.int32, device=dev)
-            nodes = torch.empty((B,), dtype=torch.int32, device=dev)
-            status = torch.empty((B, n_prog), dtype=torch.int32, device=dev)
-            rc = eng.native.mtgp_flatten(pop_dev.data_ptr(), B, T, N, ctypes.byref(libs), spec_dev.data_ptr(), n_prog,
-                                         L, prog.data_ptr(), plen.data_ptr(), nodes.data_ptr(), status.data_ptr(),
-                                         stream)
-            if rc != nat.OK:
-                raise RuntimeError(f"mtgp_flatten (parameterised) failed: {rc}")
-            worst = int(status.max().item()) if status.numel() else 0
-            if worst != 0:
-                raise ValueError(f"parameterised candidate does not flatten (status {worst})")
+            prog, plen, nodes, status = g.program_buffers(B)
+            g.flatten(pop_dev, libs, g.spec_dev(K), prog, plen, nodes, status)
+            g.check_status(status)
             th = torch.from_numpy(theta).to(dev)
             npd = torch.from_numpy(nparam).to(dev)
-            # (the general Acrobot mask keeps every lane's cost prefixes behind the partials, mtgp.h)
-            hist = d["n_save"] if d.get("fit_kof") is not None else 0
-            scratch = torch.empty((B * K * R * 2 * (1 + hist),), dtype=torch.float32, device=dev)
+            scratch = torch.empty((g.scratch_floats(B, K),), dtype=torch.float32, device=dev)
             lo_d = torch.empty((B,), dtype=torch.float32, device=dev)
             gr_d = torch.empty((B, K), dtype=torch.float32, device=dev)
-            called = grad_fn
-            # dual-number code: the register-data kernels only (SR with n_var <= 4, control with
-            # state_size <= 3); wide dynamic states interpret from LDS columns (mtgp.h ABI v21)
-            wide = eng.ff.model_id != nat.MODEL_SR and getattr(eng.ff, "state_size", 0) > 3
-            if wide:
-                self.last_jit_info = None
-            if self.use_jit and not wide and (eng.ff.model_id != nat.MODEL_SR or n_data <= 4):
-                code, nbytes = eng.grad_code_buffer(nat.grad_jit_bytes(B, n_prog, L))
-                offs = torch.empty((B * n_prog + 1,), dtype=torch.int32, device=dev)
-                info = torch.empty((2,), dtype=torch.int32, device=dev)
-                gj = nat.MtgpGradJit(code, nbytes, offs.data_ptr(), info.data_ptr())
-                jit_fn = eng.native.mtgp_sr_grad_jit if eng.ff.model_id == nat.MODEL_SR else eng.native.mtgp_ctl_grad_jit
-                called = jit_fn
-                rc = jit_fn(ctypes.byref(m), prog.data_ptr(), n_prog, L, B, th.data_ptr(), npd.data_ptr(), K,
-                            ctypes.byref(ro), scratch.data_ptr(), lo_d.data_ptr(), gr_d.data_ptr(), ctypes.byref(gj),
-                            stream)
-                self.last_jit_info = info
-            else:
-                rc = grad_fn(ctypes.byref(m), prog.data_ptr(), n_prog, L, B, th.data_ptr(), npd.data_ptr(), K,
-                             ctypes.byref(ro), scratch.data_ptr(), lo_d.data_ptr(), gr_d.data_ptr(), stream)
-            if rc != nat.OK:
-                raise RuntimeError(f"{called.__name__} rejected the configuration (code {rc})")
-            g = gr_d.cpu().numpy()
+            g.call(prog, B, th, npd, K, scratch, lo_d, gr_d, g.jit_buffers(B))
+            gr = gr_d.cpu().numpy()
             if loss is None:
                 loss = lo_d.cpu().numpy()
             for b in range(B):
-                grads[b][lo: lo + nparam[b]] = g[b, : nparam[b]]
+                grads[b][lo: lo + nparam[b]] = gr[b, : nparam[b]]
         return loss, grads
 
-    def optimise(self, candidates: np.ndarray, data, n_epoch: int, optimiser=None):
-        """gp.py:454-473 -> (fitness [B] = best loss over the epochs, candidates at that epoch)."""
+    def optimise(self, candidates, data, n_epoch: int, optimiser=None):
+        """gp.py:454-473 -> (fitness [B] = best loss over the epochs, candidates at that epoch).
+
+        The result follows the input, as evaluate_population's does.  numpy in: the host loop,
+        numpy out.  A CUDA tensor in: CUDA tensors out, and with the built-in optimiser (an `Adam`
+        itself, not a subclass or another optax-style object) the whole loop runs on the device
+        (`_optimise_device`: no candidate crosses to the host, the one read-back is the B
+        coefficient counts that size the launches); any other optimiser, or MTGP_OPT_DEVICE=0,
+        takes the host loop with the copies at its boundary."""
         opt = optimiser if optimiser is not None else adam()
+        if isinstance(candidates, torch.Tensor) and candidates.is_cuda:
+            if type(opt) is Adam and os.environ.get("MTGP_OPT_DEVICE", "1") != "0":
+                return self._optimise_device(candidates, data, n_epoch, opt)
+            fit, out = self.optimise(candidates.detach().cpu().numpy(), data, n_epoch, opt)
+            dev = candidates.device
+            return (torch.from_numpy(np.ascontiguousarray(fit, np.float32)).to(dev),
+                    torch.from_numpy(np.ascontiguousarray(out, np.float32)).to(dev))
         cands = np.array(candidates, np.float32, copy=True)
         rows = coefficient_rows(cands)
         sizes = [len(r) for r in rows]
@@ -287,3 +279,179 @@ class CoefficientOptimiser:
         best = np.argmin(L, axis=0)
         out = np.stack([hist_c[e][b] for b, e in enumerate(best)]) if len(best) else cands[:0]
         return L.min(axis=0), out
+
+    def _optimise_device(self, candidates: torch.Tensor, data, n_epoch: int, opt: Adam):
+        """`optimise` with the candidates on the GPU throughout (csrc/mtgp_optim.hip, DESIGN.md
+        "Device optimise"), the host loop's result bit for bit.  The coefficient rows never change
+        during the loop, only their values, and the gradient entry points take the values as theta:
+        with one chunk (every candidate has at most param_cap coefficient rows, the common case)
+        the candidates are parameterised and flattened once and an epoch is one gradient call and
+        one fused track + Adam step, nothing read back.  With several chunks the other chunks'
+        coefficients are literals in the programs, so parameterise + flatten repeat per epoch, on
+        the device.  Host reads: the B coefficient counts (they size K, the program specs and the
+        node library) and the flatten status, once each."""
+        if int(n_epoch) < 1:
+            raise ValueError("optimise needs at least one epoch")
+        eng = self.engine
+        dev = eng.device
+        lib = eng.native
+        cands = candidates.detach().to(dev, torch.float32).contiguous()
+        if cands.data_ptr() % 16:
+            cands = cands.clone()
+        B, T, N, four = cands.shape
+        if four != 4:
+            raise ValueError("candidate rows must have 4 columns [f, a, b, value]")
+        fit = torch.empty((B,), dtype=torch.float32, device=dev)
+        if B == 0:
+            return fit, cands.clone()
+        g = _GradContext(self, data, N)
+        stream = g.stream
+
+        def ok(rc, name):
+            if rc != nat.OK:
+                raise RuntimeError(f"{name} failed: {rc}")
+
+        work = cands.clone()  # the value column moves with every epoch; `cands` stays the input
+        rowidx = torch.empty((B, T * N), dtype=torch.int32, device=dev)
+        count = torch.empty((B,), dtype=torch.int32, device=dev)
+        ok(lib.mtgp_coef_index(work.data_ptr(), B, T, N, rowidx.data_ptr(), count.data_ptr(), stream), "mtgp_coef_index")
+        counts = count.cpu().numpy()  # the one read-back the sizing needs
+        windows = chunk_windows(counts, g.cap)
+        single = len(windows) == 1
+        M = max(1, int(counts.max()))
+        k_max = max(K for _, K in windows)
+        # every buffer of the call: programs, scratch and code are shared by the chunks (stream
+        # order), theta / nparam / gradient are per chunk (all chunks see the pre-update values)
+        pop = torch.empty_like(work)
+        prog, plen, nodes, status = g.program_buffers(B)
+        scratch = torch.empty((g.scratch_floats(B, k_max),), dtype=torch.float32, device=dev)
+        jit = g.jit_buffers(B)
+        mu = torch.empty((B, M), dtype=torch.float32, device=dev)
+        nu, best_vals = torch.empty_like(mu), torch.empty_like(mu)
+        loss = torch.empty((B,), dtype=torch.float32, device=dev)
+        loss_rest = torch.empty_like(loss)  # the other chunks' (equal) loss: the first chunk's counts
+        worst = torch.zeros((), dtype=torch.int32, device=dev)
+        chunks = []
+        for lo, K in windows:
+            chunks.append(dict(lo=lo, K=K, libs=extended_library(eng.lib, g.n_data, K), spec=g.spec_dev(K),
+                               theta=torch.empty((B, K), dtype=torch.float32, device=dev),
+                               nparam=torch.empty((B,), dtype=torch.int32, device=dev),
+                               grad=torch.empty((B, K), dtype=torch.float32, device=dev)))
+        base_lib = eng.lib.native()
+        out = torch.empty_like(work)
+
+        def programs(c):
+            ok(lib.mtgp_coef_parameterise(work.data_ptr(), B, T, N, ctypes.byref(base_lib), g.n_data, c["lo"], c["K"],
+                                          pop.data_ptr(), c["theta"].data_ptr(), c["nparam"].data_ptr(), stream),
+               "mtgp_coef_parameterise")
+            g.flatten(pop, c["libs"], c["spec"], prog, plen, nodes, status)
+
+        for epoch in range(int(n_epoch)):
+            for i, c in enumerate(chunks):
+                if epoch == 0 or not single:
+                    programs(c)
+                    if epoch == 0:
+                        g.check_status(status)
+                    else:
+                        torch.maximum(worst, status.max(), out=worst)
+                g.call(prog, B, c["theta"], c["nparam"], c["K"], scratch, loss if i == 0 else loss_rest, c["grad"], jit)
+            s = opt.scalars(epoch + 1)
+            for i, c in enumerate(chunks):
+                ok(lib.mtgp_coef_adam_step(work.data_ptr(), B, T, N, rowidx.data_ptr(), count.data_ptr(), c["lo"],
+                                           c["K"], M, c["grad"].data_ptr(), loss.data_ptr(), ctypes.byref(s),
+                                           int(epoch == 0), int(i == len(chunks) - 1), mu.data_ptr(), nu.data_ptr(),
+                                           best_vals.data_ptr(), fit.data_ptr(),
+                                           c["theta"].data_ptr() if single else None, stream), "mtgp_coef_adam_step")
+        ok(lib.mtgp_coef_scatter(cands.data_ptr(), B, T, N, M, best_vals.data_ptr(), out.data_ptr(), stream),
+           "mtgp_coef_scatter")
+        if not single and int(n_epoch) > 1:
+            g.check_status(worst)
+        return fit, out
+
+
+class _GradContext:
+    """What one gradient call needs of the engine and the data, shared by the host loop
+    (loss_and_grad) and the device loop (_optimise_device): the model and rollout structs, the
+    program specs with K parameter slots, the flatten of a parameterised population and the call of
+    the gradient entry point itself (interpreter or dual-number code)."""
+
+    def __init__(self, opt: CoefficientOptimiser, data, N: int):
+        eng = opt.engine
+        self.opt, self.eng = opt, eng
+        self.d = d = eng.prepare_data(data)
+        opt.check_data(d)
+        self.n_data = n_data = eng.ff.n_data()
+        self.specs, _ = eng._specs()
+        self.n_prog = len(self.specs)
+        self.cap = opt.param_cap(n_data)
+        self.dev = eng.device
+        self.stream = torch.cuda.current_stream(self.dev).cuda_stream
+        self.m = eng.model_struct(d)
+        self.ro = eng.rollouts_struct(d)
+        self.R = d["R"]
+        self.L = eng.program_stride(N)
+        # (the general Acrobot mask keeps every lane's cost prefixes behind the partials, mtgp.h)
+        self.hist = d["n_save"] if d.get("fit_kof") is not None else 0
+        sr = eng.ff.model_id == nat.MODEL_SR
+        self.grad_fn = opt._grad_fn()
+        self.jit_fn = eng.native.mtgp_sr_grad_jit if sr else eng.native.mtgp_ctl_grad_jit
+        # dual-number code: the register-data kernels only (SR with n_var <= 4, control with
+        # state_size <= 3); wide dynamic states interpret from LDS columns (mtgp.h ABI v21)
+        self.wide = not sr and getattr(eng.ff, "state_size", 0) > 3
+        self.use_code = opt.use_jit and not self.wide and (not sr or n_data <= 4)
+
+    def spec_dev(self, K: int) -> torch.Tensor:
+        spec_arr = (nat.MtgpProgramSpec * len(self.specs))()
+        for i, sp in enumerate(self.specs):  # the reference's data vector + K parameter slots (no slot gap)
+            spec_arr[i].tree, spec_arr[i].n_data, spec_arr[i].zero_mask = sp[0], sp[1] + K, sp[2]
+        return torch.frombuffer(bytearray(bytes(spec_arr)), dtype=torch.uint8).to(self.dev)
+
+    def program_buffers(self, B: int):
+        dev, n_prog = self.dev, self.n_prog
+        prog = torch.empty((B * n_prog * self.L * 2 + 8,), dtype=torch.int32, device=dev)
+        plen = torch.empty((B, n_prog), dtype=torch.int32, device=dev)
+        nodes = torch.empty((B,), dtype=torch.int32, device=dev)
+        status = torch.empty((B, n_prog), dtype=torch.int32, device=dev)
+        return prog, plen, nodes, status
+
+    def flatten(self, pop_dev: torch.Tensor, libs, spec_dev, prog, plen, nodes, status) -> None:
+        B, T, N, _ = pop_dev.shape
+        rc = self.eng.native.mtgp_flatten(pop_dev.data_ptr(), B, T, N, ctypes.byref(libs), spec_dev.data_ptr(),
+                                          self.n_prog, self.L, prog.data_ptr(), plen.data_ptr(), nodes.data_ptr(),
+                                          status.data_ptr(), self.stream)
+        if rc != nat.OK:
+            raise RuntimeError(f"mtgp_flatten (parameterised) failed: {rc}")
+
+    @staticmethod
+    def check_status(status: torch.Tensor) -> None:
+        worst = int(status.max().item()) if status.numel() else 0
+        if worst != 0:
+            raise ValueError(f"parameterised candidate does not flatten (status {worst})")
+
+    def scratch_floats(self, B: int, K: int) -> int:
+        return B * K * self.R * 2 * (1 + self.hist)
+
+    def jit_buffers(self, B: int):
+        """(MtgpGradJit, offsets, info) when the call runs dual-number code, else None."""
+        if self.wide:
+            self.opt.last_jit_info = None
+        if not self.use_code:
+            return None
+        code, nbytes = self.eng.grad_code_buffer(nat.grad_jit_bytes(B, self.n_prog, self.L))
+        offs = torch.empty((B * self.n_prog + 1,), dtype=torch.int32, device=self.dev)
+        info = torch.empty((2,), dtype=torch.int32, device=self.dev)
+        return nat.MtgpGradJit(code, nbytes, offs.data_ptr(), info.data_ptr()), offs, info
+
+    def call(self, prog, B: int, th, npd, K: int, scratch, loss_out, grad_out, jit) -> None:
+        """mtgp_sr_grad / mtgp_ctl_grad (jit None) or their _jit forms on the current stream."""
+        args = (ctypes.byref(self.m), prog.data_ptr(), self.n_prog, self.L, B, th.data_ptr(), npd.data_ptr(), K,
+                ctypes.byref(self.ro), scratch.data_ptr(), loss_out.data_ptr(), grad_out.data_ptr())
+        if jit is not None:
+            called = self.jit_fn
+            rc = called(*args, ctypes.byref(jit[0]), self.stream)
+            self.opt.last_jit_info = jit[2]
+        else:
+            called = self.grad_fn
+            rc = called(*args, self.stream)
+        if rc != nat.OK:
+            raise RuntimeError(f"{called.__name__} rejected the configuration (code {rc})")

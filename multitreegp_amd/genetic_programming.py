@@ -186,9 +186,11 @@ class GeneticProgramming:
         """evaluate_population of a population on the GPU: no host copy of it is made, the shards
         are device slices.  The same values as the numpy path: the fitness vector (a few KB) comes
         to the host for the best-so-far bookkeeping, which copies one candidate back; on an
-        optimising generation the 50 best are gathered to the host, optimised as there and
-        scattered into a copy on the device.  With several ranks every rank holds the whole
-        population and the all-gathered fitness (moved back to the device under gloo)."""
+        optimising generation the 50 best are gathered, optimised (CoefficientOptimiser's device
+        loop) and scattered into a copy on the device, no candidate crossing to the host (a custom
+        optimiser or MTGP_OPT_DEVICE=0: the host loop, copies at its boundary).  With several ranks
+        every rank holds the whole population and the all-gathered fitness (moved back to the device
+        under gloo), and the optimised blocks are all-gathered through numpy (sharded_rows)."""
         dev = populations.device
         P = self.num_populations * self.population_size
         flat = populations.to(torch.float32).reshape(P, *populations.shape[2:]).contiguous()
@@ -200,11 +202,20 @@ class GeneticProgramming:
             raw = raw.cpu().numpy()
             best_idx = np.argsort(raw, kind="stable")[:50]
             idx_dev = torch.from_numpy(best_idx).to(dev)
-            best = flat[idx_dev].cpu().numpy()
-            opt_fit, opt_pop = mdist.sharded_rows(
-                lambda lo, hi: self._optimise_shard(best[lo:hi], data), len(best_idx), tuple(flat.shape[1:]))
+            best = flat[idx_dev]
+            if mdist.world()[1] == 1:  # gathered, optimised and scattered on the device
+                opt_fit, opt_pop = self._optimise_shard(best, data)
+                opt_fit, opt_pop = opt_fit.cpu().numpy(), opt_pop.to(dev)
+            else:  # each rank optimises its block on its device; the all-gather's interface is numpy
+                def block(lo, hi):
+                    if hi <= lo:
+                        return np.zeros(0, np.float32), np.zeros((0,) + tuple(flat.shape[1:]), np.float32)
+                    f, c = self._optimise_shard(best[lo:hi], data)
+                    return f.cpu().numpy(), c.cpu().numpy()
+                opt_fit, opt_pop = mdist.sharded_rows(block, len(best_idx), tuple(flat.shape[1:]))
+                opt_pop = torch.from_numpy(np.ascontiguousarray(opt_pop, np.float32)).to(dev)
             flat = flat.clone()
-            flat[idx_dev] = torch.from_numpy(np.ascontiguousarray(opt_pop, np.float32)).to(dev)
+            flat[idx_dev] = opt_pop
             raw[best_idx] = opt_fit
             counts = (flat[..., 0] != 0).sum(dim=tuple(range(1, flat.ndim - 1))).cpu().numpy().astype(np.float32)
             fitness = (raw + np.float32(self.size_parsinomy) * counts).astype(np.float32)
@@ -225,8 +236,9 @@ class GeneticProgramming:
             return torch.empty((0,), dtype=torch.float32, device=eng.device)
         return eng.evaluate(flat[lo:hi].to(eng.device), data)["fitness"]
 
-    def _optimise_shard(self, cands: np.ndarray, data):
-        """GeneticProgramming.optimise (gp.py:454-473) of this rank's candidates on its GPU."""
+    def _optimise_shard(self, cands, data):
+        """GeneticProgramming.optimise (gp.py:454-473) of this rank's candidates on its GPU; the
+        result follows the input (numpy, or CUDA tensors: CoefficientOptimiser.optimise)."""
         if len(cands) == 0:
             return np.zeros(0, np.float32), cands
         opt = CoefficientOptimiser(self.vmap_foriloop.engine(self.fitness_function, 0.0))
