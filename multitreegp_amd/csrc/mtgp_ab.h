@@ -30,6 +30,10 @@
 #ifndef MTGP_FAIR_DPP
 #define MTGP_FAIR_DPP 1     // FairShare's 16-lane minimum by DPP row operations (1) or LDS shuffles (0)
 #endif
+// Dynamic JIT stage loop (round 8, DESIGN.md "Round 8"); 0 = the round-7 form:
+#ifndef MTGP_STAGE_GUARD
+#define MTGP_STAGE_GUARD 1  // one wave-uniform range test of the state per stage / save point instead of the
+#endif                      // finite, wrap and trig-range tests of the observation and the drift
 
 // ---- diagnostics (0 = shipped)
 #ifndef MTGP_AB_NOPROG

@@ -42,8 +42,10 @@
 // StirredTankReactor, MTGP_TU=6 the Acrobot kernels of the general cost mask (EnvAcrobotMask),
 // MTGP_TU=7 the fixed-step Acrobot control kernels (the C3 / C2 hot kernels: an A/B variant of
 // them recompiles this unit only, scripts/build_ab.py), MTGP_TU=8 the SR kernels, MTGP_TU=9 the
-// runtime-state-size Dopri5 control kernels (state_size 4 .. 16, round 6), behind one hidden C++
-// entry each.  Without MTGP_TU it is one monolithic TU.
+// runtime-state-size Dopri5 control kernels (state_size 4 .. 16, round 6), MTGP_TU=10 the
+// fixed-step Acrobot kernels of the static policy (the C2 hot kernel; out of unit 7 since round 8,
+// which compiles unit 7 without the SLP vectorizer -- that costs the static loop 3 %), behind one
+// hidden C++ entry each.  Without MTGP_TU it is one monolithic TU.
 #ifndef MTGP_TU
 #define MTGP_TU_MAIN 1
 #define MTGP_TU_HARMONIC 1
@@ -55,6 +57,7 @@
 #define MTGP_TU_ACRO 1
 #define MTGP_TU_SR 1
 #define MTGP_TU_DP_RT 1
+#define MTGP_TU_ACRO_STATIC 1
 #else
 #define MTGP_TU_MAIN (MTGP_TU == 0)
 #define MTGP_TU_HARMONIC (MTGP_TU == 1)
@@ -66,6 +69,7 @@
 #define MTGP_TU_ACRO (MTGP_TU == 7)
 #define MTGP_TU_SR (MTGP_TU == 8)
 #define MTGP_TU_DP_RT (MTGP_TU == 9)
+#define MTGP_TU_ACRO_STATIC (MTGP_TU == 10)
 #endif
 
 namespace {
@@ -226,6 +230,36 @@ __device__ __forceinline__ bool trig_args_small(float v) {
   return (__float_as_uint(v) & 0x7fffffffu) - 0x47000000u >= 0x38800000u;
 }
 
+// State range of the stage guard (MTGP_STAGE_GUARD): both angles below 2^15 in magnitude, both
+// velocities finite, tested on the bits (a NaN or inf angle fails the first test).  It implies
+// every component finite, |theta + pi| < 2^20 (the wraps' fast path, mtgp_fmod_2pi) and
+// trig_args_small for both angles, so a wave whose lanes all pass runs the observation and the
+// drift with those tests compiled out -- the same arithmetic in the same order.
+// `limit` is kStateSmall, or 0 (no state passes) where the caller has a wave-uniform reason of its
+// own to keep the guarded forms: ONE compare per lane, so that the vote is a ballot compare.
+constexpr int kStateSmall = 0x47000000;  // bits of 2^15
+__device__ __forceinline__ bool acro_state_small(const float x[4], int limit) {
+  const int M = 0x7fffffff;  // (the masked words are non-negative: signed and unsigned order agree)
+  const int vm = max(__float_as_int(x[2]) & M, __float_as_int(x[3]) & M);
+  // vm < 0x7f800000 (finite) <=> vm - 0x38800000 < 0x47000000: one compare for angles and velocities
+  return max(max(__float_as_int(x[0]) & M, __float_as_int(x[1]) & M), vm - 0x38800000) < limit;
+}
+// mtgp_wrap_angle for |v + pi| < 2^20 (the caller's guard): mtgp_fmod_2pi's fast path alone
+__device__ __forceinline__ float acro_wrap_fast(float v) {
+  const float b = MTGP_TWO_PI_F, a = v + MTGP_PI_F;
+  const float aa = __builtin_fabsf(a);
+  const float q = __builtin_truncf(aa * 1.59154951572418213e-01f);
+  float r = __builtin_fmaf(-q, b, aa);
+  r = (r < 0.0f) ? r + b : r;
+  r = __uint_as_float(__float_as_uint(r) | (__float_as_uint(a) & 0x80000000u));
+  r = (r < 0.0f) ? r + b : r;
+  return r - MTGP_PI_F;
+}
+
+// MODE bits (the dynamic JIT loop, DESIGN.md "Round 8"; 0 = every test in place):
+constexpr int kDriftTrigKnown = 1;  // trig_args_small holds for both angles in every lane (the stage guard)
+constexpr int kDriftDivKnown = 2;   // fastdiv is known true (folded into the stage guard)
+template <int MODE = 0>
 __device__ __forceinline__ void acro_drift(const AcroConst& k, const float x[4], float u_raw,
                                            float dx[4], bool fastdiv = false, int pc = 0) {
   (void)pc;  // (MTGP_AB_PATHCOUNT only)
@@ -249,12 +283,14 @@ __device__ __forceinline__ void acro_drift(const AcroConst& k, const float x[4],
 #if MTGP_AB_PATHCOUNT
   path_count(2, !(trig_args_small(th1) && trig_args_small(th2)), pc);
 #endif
-  if (__builtin_expect(!wave_all(trig_args_small(th1) && trig_args_small(th2)), 0)) {
-    s2 = mtgp_sinf(th2);
-    c2 = mtgp_cosf(th2);
-    s1 = mtgp_sinf(th1);
-    ca = mtgp_cosf(ea);
-    cb = mtgp_cosf(eb);
+  if constexpr (!(MODE & kDriftTrigKnown)) {
+    if (__builtin_expect(!wave_all(trig_args_small(th1) && trig_args_small(th2)), 0)) {
+      s2 = mtgp_sinf(th2);
+      c2 = mtgp_cosf(th2);
+      s1 = mtgp_sinf(th1);
+      ca = mtgp_cosf(ea);
+      cb = mtgp_cosf(eb);
+    }
   }
 #endif
 #if MTGP_AB_NODIV  // diagnostic: the four divisions as products
@@ -268,7 +304,7 @@ __device__ __forceinline__ void acro_drift(const AcroConst& k, const float x[4],
   const float phi1 = (((k.A0 * (thd2 * thd2)) * s2 - ((k.B0 * thd1) * thd2) * s1) +
                       k.C0 * cb) + phi2;
 #if !MTGP_AB_NODIV && !MTGP_AB_SLOWDIV
-  if (__builtin_expect(fastdiv, 1)) {  // wave-uniform: the denominators are safe (acro_div_ok)
+  if (__builtin_expect((MODE & kDriftDivKnown) || fastdiv, 1)) {  // wave-uniform: the denominators are safe (acro_div_ok)
     const float r1 = div_rcp(d1);
     const float num = ((control + div_by(d2, d1, r1) * phi1) - (k.m2l1lc2 * (thd1 * thd1)) * s2) - phi2;
     const float den = k.den0 - div_by(d2 * d2, d1, r1);
@@ -613,6 +649,7 @@ struct EnvAcrobot {
   // (same operations, so bit-identical) -- holding them live cost 8 VGPRs next to the JIT call
   float l1, l2, m1, m2;
   bool fastdiv;  // wave-uniform: every lane's drift denominators are in the safe range (acro_div_ok)
+  int small_limit;  // wave-uniform: stage_ok's limit (kStateSmall, or 0 = never, without fastdiv)
   typedef AcroFit Fit;
   __device__ __forceinline__ void load(const MtgpRollouts& ro, int rr, int nt) {
     (void)nt;
@@ -621,13 +658,31 @@ struct EnvAcrobot {
     m1 = ro.params[4 * rr + 2];
     m2 = ro.params[4 * rr + 3];
     fastdiv = wave_all(acro_div_ok(acro_const(l1, l2, m1, m2)));
+    small_limit = uni(fastdiv ? kStateSmall : 0);
   }
+  template <int MODE = 0>
   __device__ __forceinline__ void drift(const float x[4], float u, float dx[4], int pc = 0) const {
-    acro_drift(acro_const(l1, l2, m1, m2), x, u, dx, fastdiv, pc);
+    acro_drift<MODE>(acro_const(l1, l2, m1, m2), x, u, dx, fastdiv, pc);
   }
   __device__ __forceinline__ static void obs_transform(float y[4]) {
     y[0] = mtgp_wrap_angle(y[0]);
     y[1] = mtgp_wrap_angle(y[1]);
+  }
+  // the stage guard of the dynamic JIT loop (acro_state_small): per lane, with the launch's fastdiv
+  // folded into the limit so that the guarded-out stage needs no test of it
+  __device__ __forceinline__ bool stage_ok(const float x[4]) const { return acro_state_small(x, small_limit); }
+  // the observation of a state that passed stage_ok: x + nz and the wraps' fast path (WRAP_KNOWN: nz
+  // is +0, so |y + pi| < 2^20 follows from the guard; with observation noise the wrap keeps its test)
+  template <bool WRAP_KNOWN>
+  __device__ __forceinline__ static void obs_small(const float x[4], const float nz[4], float y[4]) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) y[i] = x[i] + nz[i];
+    if constexpr (WRAP_KNOWN) {
+      y[0] = acro_wrap_fast(y[0]);
+      y[1] = acro_wrap_fast(y[1]);
+    } else {
+      obs_transform(y);
+    }
   }
   __device__ __forceinline__ static bool bad(const float* s, int n) { return acro_bad(s, n); }
   __device__ __forceinline__ static Fit fit_init(bool active) { return Fit{!active, 0.0f, 0.0f, 0.0f}; }
@@ -1403,6 +1458,8 @@ struct FairShare {
 template <class Env, int NA, bool TRAJ, bool NOISE, int NST>
 __device__ __forceinline__ void ctl_dynamic_jit(const KArgs& A, const Lane& Ln) {
   constexpr int NV = Env::NV;
+  // one range test per stage and save point (MTGP_STAGE_GUARD; Acrobot: EnvAcrobot::stage_ok)
+  constexpr bool kGuard = MTGP_STAGE_GUARD && std::is_same<Env, EnvAcrobot>::value && !MTGP_AB_PATHCOUNT && !MTGP_AB_NOOBS;
   const int r = Ln.r, rr = Ln.rr;
   const bool active = Ln.active;
   const int R = A.ro.R;
@@ -1457,7 +1514,15 @@ __device__ __forceinline__ void ctl_dynamic_jit(const KArgs& A, const Lane& Ln) 
         nzt = tb;
       }
     }
-    ctl_obs_apply<Env>(xs, nzv, yo);  // f_obs(key, (ts[k], xs[k])), dyn.py:99
+    // f_obs(key, (ts[k], xs[k])), dyn.py:99; the stage guard on the saved state (a wave that holds
+    // a lane of the +inf fill fails it and runs the guarded form)
+    bool small = false;
+    if constexpr (kGuard) small = wave_all(env.stage_ok(xs));
+    if (kGuard && __builtin_expect(small, 1)) {
+      if constexpr (kGuard) Env::template obs_small<!NOISE>(xs, nzv, yo);
+    } else {
+      ctl_obs_apply<Env>(xs, nzv, yo);
+    }
 #pragma unroll
     for (int i = 0; i < NV; ++i) dv[i] = yo[i];
 #pragma unroll
@@ -1520,21 +1585,31 @@ __device__ __forceinline__ void ctl_dynamic_jit(const KArgs& A, const Lane& Ln) 
       }
       // one call: the readout (y, u folded: reads [0, a, 0, tar]) returns u in v26, and the state
       // programs it falls into read their u slot from there ([y, a, u, tar]) -- MtgpJitChain.put
+      // the stage guard (kGuard, above): one wave-uniform range test of xt stands for the finite
+      // test, the wraps' range tests and the drift's trig-range and fastdiv tests; a wave that
+      // fails it runs the guarded forms unchanged
+      bool small = false;
+      if constexpr (kGuard) small = wave_all(env.stage_ok(xt));
+      if (kGuard && __builtin_expect(small, 1)) {
+        if constexpr (kGuard) Env::template obs_small<!NOISE>(xt, nzv, y);
+      } else {
 #if MTGP_AB_PATHCOUNT
-      ctl_obs_apply<Env>(xt, nzv, y, dead ? 2 : 1);
+        ctl_obs_apply<Env>(xt, nzv, y, dead ? 2 : 1);
 #else
-      ctl_obs_apply<Env>(xt, nzv, y);
+        ctl_obs_apply<Env>(xt, nzv, y);
 #endif
+      }
 #pragma unroll
       for (int i = 0; i < NV; ++i) dv[i] = y[i];
       const ChainOut c = jit_call_chain_nf(u_readout, dv, 0);
 #pragma unroll
       for (int j = 0; j < NA; ++j) ka[j] = c.v[1 + j < mtgp::kJitChainMax ? 1 + j : 0];
-#if MTGP_AB_PATHCOUNT
-      if constexpr (std::is_same<Env, EnvAcrobot>::value) env.drift(xt, c.v[0], kx, dead ? 2 : 1);
-      else
-#endif
-      env.drift(xt, c.v[0], kx);
+      if constexpr (std::is_same<Env, EnvAcrobot>::value) {
+        if (kGuard && __builtin_expect(small, 1)) env.template drift<kDriftTrigKnown | kDriftDivKnown>(xt, c.v[0], kx);
+        else env.drift(xt, c.v[0], kx, MTGP_AB_PATHCOUNT ? (dead ? 2 : 1) : 0);
+      } else {
+        env.drift(xt, c.v[0], kx);
+      }
       if (ST == 0) {
 #pragma unroll
         for (int i = 0; i < NV; ++i) fx0[i] = kx[i];
@@ -5106,6 +5181,9 @@ int launch_dp_entry(MTGP_TU_DP_ARGS) {
   else return mtgp_tu_launch_reactor_dopri5(A, model, jit, noise, traj, grid, block, s);
 }
 
+// the fixed-step static-policy Acrobot kernels' unit (MTGP_TU 10)
+__attribute__((visibility("hidden"))) int mtgp_tu_launch_acrobot_static(const void* A, bool jit, bool noise, bool traj,
+                                                                         unsigned grid, unsigned block, hipStream_t s);
 // dynamic / static evaluator on environment Env: shape checks, then the kernel variant
 template <class Env>
 int launch_ctl(const KArgs& A, const MtgpModel* model, const MtgpRollouts* ro, bool jit, bool noise, bool traj,
@@ -5146,7 +5224,12 @@ int launch_ctl(const KArgs& A, const MtgpModel* model, const MtgpRollouts* ro, b
     }, s);
     return rc != MTGP_OK ? rc : lr;
   }
-  if (model->model == MTGP_MODEL_STATIC) return launch_timed([&] { MTGP_CTL_VARIANTS(k_ctl_static, Env); }, s);
+  if (model->model == MTGP_MODEL_STATIC) {
+    if constexpr (std::is_same<Env, EnvAcrobot>::value)  // (a unit of its own: MTGP_TU 10)
+      return mtgp_tu_launch_acrobot_static(&A, jit, noise, traj, grid.x, block.x, s);
+    else
+      return launch_timed([&] { MTGP_CTL_VARIANTS(k_ctl_static, Env); }, s);
+  }
   switch (model->state_size) {
     case 1: return launch_dyn<Env, 1>(A, jit, noise, traj, grid, block, s);
     case 2: return launch_dyn<Env, 2>(A, jit, noise, traj, grid, block, s);
@@ -5216,6 +5299,14 @@ extern "C" int mtgp_ab_fb_count(unsigned long long* host) {  // diagnostic build
 #if MTGP_TU_ACRO
 int mtgp_tu_launch_acrobot(MTGP_TU_ENTRY_ARGS) {  // fixed-step solvers (Dopri5 goes on to TU 3)
   return launch_ctl<EnvAcrobot>(*(const KArgs*)A, model, ro, jit, noise, traj, dim3(grid), dim3(block), s);
+}
+#endif
+#if MTGP_TU_ACRO_STATIC
+int mtgp_tu_launch_acrobot_static(const void* Ap, bool jit, bool noise, bool traj, unsigned grid_, unsigned block_,
+                                  hipStream_t s) {
+  const KArgs& A = *(const KArgs*)Ap;
+  const dim3 grid(grid_), block(block_);
+  return launch_timed([&] { MTGP_CTL_VARIANTS(k_ctl_static, EnvAcrobot); }, s);
 }
 #endif
 #if MTGP_TU_ACRO_MASK

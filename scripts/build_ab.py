@@ -5,7 +5,11 @@ is recompiled with the variant's defines; the other units' objects are the produ
 multitreegp_amd/lib/abrun/libmtgp_hip_<name>.so (delete the directory after the GPU run: it is
 pushed with the tree).
 
-usage: build_ab.py name=DEF[,DEF...] [name=...]      e.g. notrig=MTGP_AB_NOTRIG=1"""
+A token that starts with "-" is a compiler flag instead of a define; it comes after the unit's own
+flags (__graft_entry__.HIP_TU_FLAGS), so "-fslp-vectorize" undoes the unit's -fno-slp-vectorize.
+An empty list ("name=") rebuilds the unit as shipped.
+
+usage: build_ab.py name=DEF[,DEF...] [name=...]      e.g. notrig=MTGP_AB_NOTRIG=1 slp=-fslp-vectorize"""
 import os
 import subprocess
 import sys
@@ -24,7 +28,9 @@ def build(name, defines):
     os.makedirs(vdir, exist_ok=True)
     obj0 = os.path.join(vdir, f"mtgp_kernels_tu{TU}.o")
     cflags = [f for f in g.HIPCC_FLAGS if f != "-shared"]
-    cmd = ["/opt/rocm/bin/hipcc", *cflags, "-c", f"-DMTGP_TU={TU}", *[f"-D{d}" for d in defines],
+    flags = [d for d in defines if d.startswith("-")]
+    cmd = ["/opt/rocm/bin/hipcc", *cflags, *g.HIP_TU_FLAGS.get(TU, []), *flags, "-c", f"-DMTGP_TU={TU}",
+           *[f"-D{d}" for d in defines if d and not d.startswith("-")],
            "-I", os.path.join(ROOT, "include"), "-I", g.CSRC, os.path.join(g.CSRC, "mtgp_kernels.hip"), "-o", obj0]
     return subprocess.Popen(cmd), obj0, objdir
 
@@ -41,7 +47,8 @@ def main():
         if p.wait() != 0:
             raise SystemExit(f"hipcc failed for {name}")
         objs = [obj0] + [os.path.join(objdir, f"mtgp_kernels_tu{tu}.o") for tu in g.HIP_TUS if tu != TU] + \
-               [os.path.join(objdir, "mtgp_grad.o"), os.path.join(objdir, "mtgp_build_info.o")]  # (the
+               [os.path.join(objdir, os.path.basename(x).replace(".hip", ".o")) for x in g.HIP_EXTRA] + \
+               [os.path.join(objdir, "mtgp_build_info.o")]  # (the
         # product's build info: a variant reports the product's sources hash)
         out = os.path.join(out_dir, f"libmtgp_hip_{name}.so")
         subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-fPIC", "-shared", *objs, "-o", out,
