@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define MTGP_ABI_VERSION 23
+#define MTGP_ABI_VERSION 24
 
 /* ---------------------------------------------------------------- limits */
 #define MTGP_MAX_FUNCS 128   /* node functions 2 + K + V (gp.py:135-199)       */
@@ -163,6 +163,9 @@ typedef struct {
    * t += dt0 with diffrax's end clip, each step over dt = tn - t, SaveAt(ts) for ANY non-decreasing
    * ts through the solver's dense output (RK4: cubic Hermite, Euler: linear), at most max_steps
    * steps (0: no limit) -- the unsaved points are then +inf (throw=False).
+   * MTGP_SOLVER_HEUN, _MIDPOINT, _RALSTON, _BOSH3 (ABI v24): diffrax's two-stage solvers and its
+   * FSAL Bosh3 on the same fixed-step grid, dense output cubic Hermite (include/mtgp_cstep.h);
+   * evaluation only -- mtgp_sr_grad* / mtgp_ctl_grad* return MTGP_ERR_ARG for them.
    * MTGP_SOLVER_DOPRI5: diffrax.Dopri5 + PIDController(rtol, atol, dtmin, dtmax) from dt0 = h
    * with SaveAt(ts) and at most max_steps step attempts (include/mtgp_dopri5.h, the notebooks'
    * setting, e.g. SymbolicRegression.ipynb:136); n_steps / save_every are ignored.  Implemented
@@ -188,7 +191,15 @@ typedef struct {
    * 0: one launch. */
   int32_t dp_budget;
 } MtgpModel;
-enum { MTGP_SOLVER_RK4 = 0, MTGP_SOLVER_DOPRI5 = 1, MTGP_SOLVER_EULER = 2 };
+enum {
+  MTGP_SOLVER_RK4 = 0,
+  MTGP_SOLVER_DOPRI5 = 1,
+  MTGP_SOLVER_EULER = 2,
+  MTGP_SOLVER_HEUN = 3,
+  MTGP_SOLVER_MIDPOINT = 4,
+  MTGP_SOLVER_RALSTON = 5,
+  MTGP_SOLVER_BOSH3 = 6
+};
 
 typedef struct {
   const float* x0;      /* [R, n_var]                                       */

@@ -1,6 +1,7 @@
 /*
  * mtgp_cstep.h -- fp32 arithmetic spec of the fixed-step solve: diffrax.ConstantStepSize with the
- * Euler or classical RK4 solver, SaveAt(ts) through the solver's dense output (ABI v18).
+ * Euler or classical RK4 solver (ABI v18) or with Heun, Midpoint, Ralston or Bosh3 (ABI v24),
+ * SaveAt(ts) through the solver's dense output.
  *
  * The reference evaluators integrate with
  *     diffeqsolve(ODETerm(_drift), solver, ts[0], ts[-1], dt0, y0, saveat=SaveAt(ts),
@@ -51,6 +52,34 @@
  *   so a save on a step end is the interpolant at theta = 1, not the step's y1 bit for bit.
  * Event: after a step whose y1 turns the condition negative the solve ends; that step's saves are
  *   written first, the later ones are +inf.
+ *
+ * Heun, Midpoint, Ralston, Bosh3 (ABI v24).  diffrax's published explicit Runge-Kutta solvers under
+ * ConstantStepSize, restated with the caveat above (diffrax is absent, no version is pinned: not a
+ * quotation).  The time grid, dt = tn - t, SaveAt, the event and the max_steps rules are the ones
+ * above.  Tableau entries are the float32 roundings of the double values (as MTGP_RK4_B0):
+ *   solver    c             a (lower rows)                    b_sol                 FSAL
+ *   Heun      1             [1]                               1/2, 1/2              no
+ *   Midpoint  1/2           [1/2]                             0, 1                  no
+ *   Ralston   3/4           [3/4]                             1/3, 2/3              no
+ *   Bosh3     1/2, 3/4, 1   [1/2]; [0, 3/4]; [2/9, 1/3, 4/9]  2/9, 1/3, 4/9, 0      yes
+ * Stage time t + c_i dt (the product rounds, then the sum; 1.0f dt included); stage input
+ * y + (sum_j a_ij f_j) dt, ascending j, products and sums rounded separately.  Zero entries follow
+ * the RK4 rule: a +-0 term is a no-op, a NaN term (a non-finite f_j) makes the row NaN -- Midpoint's
+ * y1 = y + [0 f0; 1 f1] dt and Bosh3's stage 2, y + [0 f0; 0.75 f1] dt.
+ *   two stages  f0 = f(t, y);  f1 = f(t + c dt, y + (a f0) dt);  y1 = y + (b0 f0 + b1 f1) dt
+ *   Bosh3       f0 = f(t, y) on the first step, the previous step's f3 afterwards (FSAL: reused,
+ *               not evaluated again, so its observation noise is the draw at t + 1.0f dt of the
+ *               step that computed it -- the convention of mtgp_dopri5.h)
+ *               f1 = f(t + 0.5 dt, y + (0.5 f0) dt)
+ *               f2 = f(t + 0.75 dt, y + [0 f0; 0.75 f1] dt)
+ *               y1 = y + ((b0 f0 + b1 f1) + b2 f2) dt    "solution same as last stage input": y1 IS
+ *               f3 = f(t + 1.0 dt, y1)                    the stage-3 input; there is no 0 f3 term
+ * Dense output, all four: ThirdOrderHermitePolynomialInterpolation.from_k, mtgp_cs_hermite with
+ * k0 = f_first dt and k1 = f_last dt -- Heun's f(t + dt, .), Midpoint's and Ralston's interior
+ * stage (literally), Bosh3's f3.
+ * As for RK4 the kernels carry only the previous stage's derivative and the running b-weighted sum
+ * (mtgp_erk2_*, mtgp_bosh3_*): a zero-weighted f0 is tested through b0 f0, which is +-0 or NaN for
+ * b0 = 0 (Midpoint) and non-finite exactly when f0 is for b0 = 2/9 (Bosh3, no overflow).
  */
 #ifndef MTGP_CSTEP_H
 #define MTGP_CSTEP_H
@@ -135,5 +164,51 @@ MTGP_INLINE MTGP_HD float mtgp_rk4_acc(int st, float acc, float f) {
 }
 /* the step's end state from the full sum */
 MTGP_INLINE MTGP_HD float mtgp_rk4_out(float y, float acc, float dt) { return y + acc * dt; }
+
+/* ---- two-stage solvers (Heun, Midpoint, Ralston): one tableau (c, a, b0, b1) each */
+typedef struct {
+  float c, a, b0, b1;
+} MtgpErk2;
+/* which = 0 Heun, 1 Midpoint, 2 Ralston (MTGP_SOLVER_HEUN + which) */
+MTGP_INLINE MTGP_HD MtgpErk2 mtgp_erk2_tableau(int which) {
+  MtgpErk2 T;
+  if (which == 0) {
+    T.c = 1.0f, T.a = 1.0f, T.b0 = 0.5f, T.b1 = 0.5f;
+  } else if (which == 1) {
+    T.c = 0.5f, T.a = 0.5f, T.b0 = 0.0f, T.b1 = 1.0f;
+  } else {
+    T.c = 0.75f, T.a = 0.75f, T.b0 = (float)(1.0 / 3.0), T.b1 = (float)(2.0 / 3.0);
+  }
+  return T;
+}
+MTGP_INLINE MTGP_HD float mtgp_erk2_time(MtgpErk2 T, float t, float dt) { return t + T.c * dt; }
+/* stage-1 input from f0 */
+MTGP_INLINE MTGP_HD float mtgp_erk2_in(MtgpErk2 T, float y, float f0, float dt) { return y + (T.a * f0) * dt; }
+/* the b-weighted sum: acc0 = b0 f0 after stage 0, then b1 f1 joins; b0 = 0: [0 f0; b1 f1] */
+MTGP_INLINE MTGP_HD float mtgp_erk2_acc0(MtgpErk2 T, float f0) { return T.b0 * f0; }
+MTGP_INLINE MTGP_HD float mtgp_erk2_acc1(MtgpErk2 T, float acc0, float f1) {
+  return T.b0 == 0.0f ? mtgp_rk4_nz(acc0, T.b1 * f1) : acc0 + T.b1 * f1;
+}
+
+/* ---- Bosh3 */
+#define MTGP_BOSH3_B0 ((float)(2.0 / 9.0))
+#define MTGP_BOSH3_B1 ((float)(1.0 / 3.0))
+#define MTGP_BOSH3_B2 ((float)(4.0 / 9.0))
+/* stage time for stage st = 1, 2, 3 (c = 0.5, 0.75, 1.0) */
+MTGP_INLINE MTGP_HD float mtgp_bosh3_time(int st, float t, float dt) {
+  return st == 1 ? t + 0.5f * dt : st == 2 ? t + 0.75f * dt : t + 1.0f * dt;
+}
+/* running b-weighted sum after stage st = 0, 1, 2 (stage 3's derivative has no term) */
+MTGP_INLINE MTGP_HD float mtgp_bosh3_acc(int st, float acc, float f) {
+  return st == 0 ? MTGP_BOSH3_B0 * f : acc + (st == 1 ? MTGP_BOSH3_B1 : MTGP_BOSH3_B2) * f;
+}
+/* stage input for stage st = 1, 2, 3 from f = f_{st-1} and acc = the sum through stage st - 2
+ * (as mtgp_rk4_in_acc): stage 2 tests b0 f0 for the zero entry, stage 3's input is the step's end
+ * state y + acc2 dt with acc2 = mtgp_bosh3_acc(2, acc, f), bit for bit mtgp_rk4_out of that sum */
+MTGP_INLINE MTGP_HD float mtgp_bosh3_in_acc(int st, float y, float f, float acc, float dt) {
+  if (st == 1) return y + (0.5f * f) * dt;
+  if (st == 2) return y + (mtgp_isfinite(acc) ? 0.75f * f : mtgp_u2f(0x7fc00000u)) * dt;
+  return y + mtgp_bosh3_acc(2, acc, f) * dt;
+}
 
 #endif /* MTGP_CSTEP_H */

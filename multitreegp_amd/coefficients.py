@@ -180,7 +180,8 @@ class CoefficientOptimiser:
     def check_evaluator(ff):
         kind = getattr(ff, "solver_kind", "")
         if kind not in ("rk4", "euler", "dopri5"):
-            raise NotImplementedError(f"coefficient optimisation: solver {kind!r}")
+            raise NotImplementedError(f"coefficient optimisation: solver {kind!r} has no gradient kernels "
+                                      "(implemented: euler, rk4, dopri5)")
         # (ABI v21: the dynamic evaluator's own limit; its constructor refuses more)
         if ff.model_id != nat.MODEL_SR and getattr(ff, "state_size", 0) > nat.GRAD_MAX_STATE:
             raise NotImplementedError(f"coefficient optimisation of the dynamic evaluator: state_size <= "

@@ -1058,6 +1058,126 @@ __device__ __forceinline__ void cs_dense(bool euler, bool dead, const float (&y)
   }
 }
 
+// The fixed-step schemes (mtgp_cstep.h), each named by its number of stages: Euler, the two-stage
+// family (Heun, Midpoint, Ralston: one code path, the tableau read as wave-uniform scalars), Bosh3
+// (three evaluations per step; its fourth stage f3 is the next step's f0, FSAL) and classical RK4.
+constexpr int kSchEuler = 1, kSchErk2 = 2, kSchBosh3 = 3, kSchRk4 = 4;
+__host__ __device__ __forceinline__ bool cs_is_erk(int solver) { return solver >= MTGP_SOLVER_HEUN && solver <= MTGP_SOLVER_BOSH3; }
+__device__ __forceinline__ MtgpErk2 cs_erk2_tableau(int solver) {
+  return mtgp_erk2_tableau(uni(solver) - MTGP_SOLVER_HEUN);
+}
+// The rolled stage loops' forms for the two-stage family and Bosh3 (sch = kSchErk2 / kSchBosh3,
+// wave-uniform), as stage_in_n / stage_acc_n / stage_time: the input of stage `stage` from
+// f = f_{stage-1} and acc = the b-weighted sum through stage - 2, and the sum after stage `stage`
+template <int N>
+__device__ __forceinline__ void erk_in_n(int sch, const MtgpErk2& T, int stage, const float (&s)[N], const float (&f)[N],
+                                         const float (&acc)[N], float dt, float (&out)[N]) {
+  const int st = uni(stage);
+  if (st == 0) {
+#pragma unroll
+    for (int i = 0; i < N; ++i) out[i] = s[i];
+  } else if (sch == kSchErk2) {
+#pragma unroll
+    for (int i = 0; i < N; ++i) out[i] = mtgp_erk2_in(T, s[i], f[i], dt);
+  } else if (st == 1) {
+#pragma unroll
+    for (int i = 0; i < N; ++i) out[i] = mtgp_bosh3_in_acc(1, s[i], f[i], acc[i], dt);
+  } else if (st == 2) {
+#pragma unroll
+    for (int i = 0; i < N; ++i) out[i] = mtgp_bosh3_in_acc(2, s[i], f[i], acc[i], dt);
+  } else {
+#pragma unroll
+    for (int i = 0; i < N; ++i) out[i] = mtgp_bosh3_in_acc(3, s[i], f[i], acc[i], dt);
+  }
+}
+__device__ __forceinline__ float erk_acc(int sch, const MtgpErk2& T, int st, float acc, float f) {
+  if (sch == kSchErk2) return st == 0 ? mtgp_erk2_acc0(T, f) : mtgp_erk2_acc1(T, acc, f);
+  return st == 0 ? mtgp_bosh3_acc(0, acc, f) : st == 1 ? mtgp_bosh3_acc(1, acc, f) : mtgp_bosh3_acc(2, acc, f);
+}
+template <int N>
+__device__ __forceinline__ void erk_acc_n(int sch, const MtgpErk2& T, int stage, float (&acc)[N], const float (&f)[N]) {
+  const int st = uni(stage);
+#pragma unroll
+  for (int i = 0; i < N; ++i) acc[i] = erk_acc(sch, T, st, acc[i], f[i]);
+}
+__device__ __forceinline__ float erk_in(int sch, const MtgpErk2& T, int st, float s, float f, float acc, float dt) {
+  return sch == kSchErk2 ? mtgp_erk2_in(T, s, f, dt) : mtgp_bosh3_in_acc(st, s, f, acc, dt);
+}
+__device__ __forceinline__ float erk_time(int sch, const MtgpErk2& T, int stage, float t, float dt) {
+  return stage == 0 ? t : sch == kSchErk2 ? mtgp_erk2_time(T, t, dt) : mtgp_bosh3_time(stage, t, dt);
+}
+
+// The scheme of a rolled stage loop.  ERK false: Euler / RK4, every member is the call the loops
+// always made (stage_in_n, stage_acc_n, stage_time, ...).  ERK true: the two-stage family or Bosh3,
+// scheme and tableau wave-uniform.
+template <bool ERK>
+struct CsRolled {
+  bool euler;  // diffrax.Euler: one stage, y + f dt
+  int n_stages, sch;
+  MtgpErk2 T;
+  __device__ __forceinline__ void init(int solver) {
+    if constexpr (ERK) {
+      euler = false;
+      sch = uni(solver) == MTGP_SOLVER_BOSH3 ? kSchBosh3 : kSchErk2;
+      n_stages = sch == kSchBosh3 ? 4 : 2;
+      T = cs_erk2_tableau(solver);
+    } else {
+      euler = solver == MTGP_SOLVER_EULER;
+      n_stages = euler ? 1 : 4;
+    }
+  }
+  // the step's first stage: 0, or 1 on a Bosh3 step after the first (FSAL: f0 is the last step's f3,
+  // which the caller's derivative registers still hold)
+  __device__ __forceinline__ int first_stage(int steps) const {
+    if constexpr (ERK) return (sch == kSchBosh3 && uni(steps) > 0) ? 1 : 0;
+    else return 0;
+  }
+  // stage input from f = f_{stage-1} and acc = the b-weighted sum through stage - 2
+  template <int N>
+  __device__ __forceinline__ void in(int stage, const float (&s)[N], const float (&f)[N], const float (&acc)[N], float dt,
+                                     float (&out)[N]) const {
+    if constexpr (ERK) erk_in_n<N>(sch, T, stage, s, f, acc, dt, out);
+    else stage_in_n<N>(stage, s, f, acc, dt, out);
+  }
+  __device__ __forceinline__ float in1(int stage, float s, float f, float acc, float dt) const {
+    if constexpr (ERK) return stage == 0 ? s : erk_in(sch, T, stage, s, f, acc, dt);
+    else return stage_in(stage, s, f, acc, dt);
+  }
+  // the b-weighted sum after stage `stage`'s derivative f
+  template <int N>
+  __device__ __forceinline__ void acc(int stage, float (&a)[N], const float (&f)[N]) const {
+    if constexpr (ERK) erk_acc_n<N>(sch, T, stage, a, f);
+    else stage_acc_n<N>(stage, a, f);
+  }
+  __device__ __forceinline__ float acc1(int stage, float a, float f) const {
+    if constexpr (ERK) return erk_acc(sch, T, stage, a, f);
+    else return stage_acc(stage, a, f);
+  }
+  // stage `stage`'s derivative has a term in the sum (Bosh3's f3 has none: its input was the end state)
+  __device__ __forceinline__ bool has_term(int stage) const {
+    if constexpr (ERK) return !(sch == kSchBosh3 && stage == 3);
+    else return true;
+  }
+  // the last stage's term, after the stage loop
+  template <int N>
+  __device__ __forceinline__ void finish(float (&a)[N], const float (&f)[N]) const {
+    if (has_term(n_stages - 1)) acc<N>(n_stages - 1, a, f);
+  }
+  __device__ __forceinline__ float finish1(float a, float f) const { return has_term(n_stages - 1) ? acc1(n_stages - 1, a, f) : a; }
+  // the stage's observation noise is drawn anew (RK4's stages 1 and 2 share the time t + dt/2, hence the draw)
+  __device__ __forceinline__ bool draws(int stage) const { return ERK || stage != 2; }
+  __device__ __forceinline__ float time(int stage, float t, float dt) const {
+    if constexpr (ERK) return erk_time(sch, T, stage, t, dt);
+    else return stage_time(stage, t, dt);
+  }
+  // a lane whose solve has ended (MTGP_DEAD_ZERO): Bosh3 reuses the last derivative, which is that of
+  // the non-finite end state, so it is cleared with the state; Euler / RK4 restart from f(0)
+  template <int N>
+  __device__ __forceinline__ void dead_clear(float (&f)[N]) const {
+    if constexpr (ERK) dead_state_clear<N>(f);
+  }
+};
+
 // --------------------------------------------------------------------------------------
 // The data vector a tree reads and its operand stack.  Interpreter: one LDS column per slot
 // (dcol, st).  JIT: the slots live in VGPRs v[] that the call site pins to v0-v7
@@ -1369,6 +1489,36 @@ __device__ __forceinline__ void rk_acc(int st, float (&acc)[N], const float (&f)
   for (int i = 0; i < N; ++i) acc[i] = mtgp_rk4_acc(st, acc[i], f[i]);
 }
 
+// The unrolled loops' forms by scheme NST (kSchEuler / kSchRk4: exactly rk_in / rk_acc, T unused):
+// the input of stage st, the b-weighted sum after stage st's derivative f, the stage time
+template <int NST, int N>
+__device__ __forceinline__ void cs_in(int st, const MtgpErk2& T, const float (&s)[N], const float (&f)[N],
+                                      const float (&acc)[N], float dt, float (&out)[N]) {
+  if constexpr (NST == kSchErk2) {
+#pragma unroll
+    for (int i = 0; i < N; ++i) out[i] = st == 0 ? s[i] : mtgp_erk2_in(T, s[i], f[i], dt);
+  } else if constexpr (NST == kSchBosh3) {
+#pragma unroll
+    for (int i = 0; i < N; ++i) out[i] = st == 0 ? s[i] : mtgp_bosh3_in_acc(st, s[i], f[i], acc[i], dt);
+  } else {
+    rk_in<N>(st, s, f, acc, dt, out);
+  }
+}
+template <int NST, int N>
+__device__ __forceinline__ void cs_acc(int st, const MtgpErk2& T, float (&acc)[N], const float (&f)[N]) {
+  if constexpr (NST == kSchErk2 || NST == kSchBosh3) {
+#pragma unroll
+    for (int i = 0; i < N; ++i) acc[i] = erk_acc(NST, T, st, acc[i], f[i]);
+  } else {
+    rk_acc<N>(st, acc, f);
+  }
+}
+template <int NST>
+__device__ __forceinline__ float cs_time(int st, const MtgpErk2& T, float t, float dt) {
+  if constexpr (NST == kSchErk2 || NST == kSchBosh3) return erk_time(NST, T, st, t, dt);
+  else return st == 0 ? t : mtgp_rk4_time(st, t, dt);
+}
+
 // one JIT unit call, no fallback (the templates never request one)
 __device__ __forceinline__ float jit_call_nf(uint64_t addr_, const float d[kDMax]) {
   uint64_t fl = 0;
@@ -1561,25 +1711,28 @@ __device__ __forceinline__ void ctl_dynamic_jit(const KArgs& A, const Lane& Ln) 
   const bool fair_on = uni(A.fair) != 0;
   FairShare fair;
   if (fair_on) fair.init(A);
+  MtgpErk2 T{};  // the two-stage family's tableau (wave-uniform; NST = kSchErk2 only)
+  if constexpr (NST == kSchErk2) T = cs_erk2_tableau(A.m.solver);
   while (clk.live()) {
     if (fair_on) fair.step(Ln.lane, (uint32_t)clk.steps);
     const float t = clk.t, dt = clk.dt();
-    // one RK stage (NST = 4) or the Euler step (NST = 1); ST is a compile-time constant.  The
+    // one RK stage (NST = 4, or 2 / 3: the two-stage family / Bosh3) or the Euler step (NST = 1);
+    // ST is a compile-time constant.  The
     // stage input reads the b-weighted sum before f_{ST-1}'s term (mtgp_rk4_in_acc: the zero
     // tableau entries, mtgp_cstep.h), which is then added -- the same sums in the same order.
     auto stage = [&](auto st_c) {
       constexpr int ST = decltype(st_c)::value;
       float xt[NV], at[NA], y[NV];
-      rk_in<NV>(ST, x, kx, ax, dt, xt);
-      rk_in<NA>(ST, a, ka, aa, dt, at);
-      if (NST == 4 && ST > 0) {
-        rk_acc<NV>(ST - 1, ax, kx);
-        rk_acc<NA>(ST - 1, aa, ka);
+      cs_in<NST, NV>(ST, T, x, kx, ax, dt, xt);
+      cs_in<NST, NA>(ST, T, a, ka, aa, dt, at);
+      if (NST != 1 && ST > 0) {
+        cs_acc<NST, NV>(ST - 1, T, ax, kx);
+        cs_acc<NST, NA>(ST - 1, T, aa, ka);
       }
 #pragma unroll
       for (int j = 0; j < NA; ++j) dv[NV + j] = at[j];
-      if (NOISE && ST != 2) {  // stages 1 and 2 share the time t + dt/2, hence the noise draw
-        const float tc = ST == 0 ? t : mtgp_rk4_time(ST, t, dt);
+      if (NOISE && (NST != 4 || ST != 2)) {  // RK4's stages 1 and 2 share the time t + dt/2, hence the noise draw
+        const float tc = cs_time<NST>(ST, T, t, dt);
         obs_noise_vec<NV>(nzc, tc, nzv);
         nzt = __float_as_uint(tc);
       }
@@ -1617,13 +1770,32 @@ __device__ __forceinline__ void ctl_dynamic_jit(const KArgs& A, const Lane& Ln) 
         for (int j = 0; j < NA; ++j) fa0[j] = ka[j];
       }
     };
-    stage(std::integral_constant<int, 0>{});
+    if constexpr (NST == kSchBosh3) {  // FSAL: after the first step f0 is the last step's f3 (still in kx, ka)
+      if (uni(clk.steps) == 0) {
+        stage(std::integral_constant<int, 0>{});
+      } else {
+#pragma unroll
+        for (int i = 0; i < NV; ++i) fx0[i] = kx[i];
+#pragma unroll
+        for (int j = 0; j < NA; ++j) fa0[j] = ka[j];
+      }
+      stage(std::integral_constant<int, 1>{});
+      stage(std::integral_constant<int, 2>{});
+      stage(std::integral_constant<int, 3>{});  // its input is the step's end state: no term for f3
+    } else {
+      stage(std::integral_constant<int, 0>{});
+    }
     if constexpr (NST == 4) {
       stage(std::integral_constant<int, 1>{});
       stage(std::integral_constant<int, 2>{});
       stage(std::integral_constant<int, 3>{});
       rk_acc<NV>(3, ax, kx);
       rk_acc<NA>(3, aa, ka);
+    }
+    if constexpr (NST == kSchErk2) {
+      stage(std::integral_constant<int, 1>{});
+      cs_acc<NST, NV>(1, T, ax, kx);
+      cs_acc<NST, NA>(1, T, aa, ka);
     }
     // the step's end state and the event (Event(cond_fn_nan) after the step, dyn.py:94)
     float x1[NV], a1[NA];
@@ -1663,6 +1835,10 @@ __device__ __forceinline__ void ctl_dynamic_jit(const KArgs& A, const Lane& Ln) 
       if (MTGP_DEAD_ZERO) {  // nothing reads this lane's state again (dead_state_clear)
         dead_state_clear<NV>(x);
         dead_state_clear<NA>(a);
+        if constexpr (NST == kSchBosh3) {  // (the reused f3 is the non-finite end state's)
+          dead_state_clear<NV>(kx);
+          dead_state_clear<NA>(ka);
+        }
       }
     }
     clk.advance();
@@ -1710,7 +1886,9 @@ struct WaveTimer {
 };
 #endif
 
-template <class Env, int NA, bool TRAJ, bool NOISE, bool JIT>
+// ERK: the kernels of the two-stage family and Bosh3 (MTGP_SOLVER_HEUN .. _BOSH3), apart from the
+// Euler / RK4 ones, whose code the new solvers so leave exactly as it was.
+template <class Env, int NA, bool ERK, bool TRAJ, bool NOISE, bool JIT>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((NA > kNaRuntime || (JIT && NA > 3)) ? 2 : 4))) k_ctl_dynamic(KArgs A) {
 #if MTGP_AB_WAVETIME
   WaveTimer wave_timer;
@@ -1727,8 +1905,13 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((NA > 
   if (JIT) asm volatile("s_icache_inv");  // the JIT code was written by an earlier kernel
   if constexpr (JIT && NA <= 3) {
     if (__builtin_expect(Ln.jok && A.chain_merge, 1)) {  // usable put-chain code: the JIT-only loop
+      if constexpr (ERK) {
+        if (A.m.solver == MTGP_SOLVER_BOSH3) ctl_dynamic_jit<Env, NA, TRAJ, NOISE, kSchBosh3>(A, Ln);
+        else ctl_dynamic_jit<Env, NA, TRAJ, NOISE, kSchErk2>(A, Ln);
+      } else {
       if (A.m.solver == MTGP_SOLVER_EULER) ctl_dynamic_jit<Env, NA, TRAJ, NOISE, 1>(A, Ln);
       else ctl_dynamic_jit<Env, NA, TRAJ, NOISE, 4>(A, Ln);
+      }
       return;
     }
   }
@@ -1815,8 +1998,6 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((NA > 
     }
   };
 
-  const bool euler = A.m.solver == MTGP_SOLVER_EULER;  // diffrax.Euler: one stage, y + f dt
-  const int n_stages = euler ? 1 : 4;
   CsClock clk;
   clk.init(A);
   int k = 0;  // next save point
@@ -1824,18 +2005,29 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((NA > 
     dead_state_clear<NV>(x);
     dead_state_clear<NA>(a);
   }
+  CsRolled<ERK> rk;  // Euler / RK4, or (ERK) the two-stage family and Bosh3
+  rk.init(A.m.solver);
+  const bool euler = rk.euler;
+  const int n_stages = rk.n_stages;
   while (clk.live()) {
     const float t = clk.t, dt = clk.dt();
+    const int stage0 = rk.first_stage(clk.steps);
+    if (stage0 != 0) {  // Bosh3 after the first step: f0 is the last step's f3 (still in kx, ka)
+#pragma unroll
+      for (int i = 0; i < NV; ++i) fx0[i] = kx[i];
+#pragma unroll
+      for (int j = 0; j < NA; ++j) fa0[j] = ka[j];
+    }
     // (the stage input reads the b-weighted sum before f_{stage-1}'s term -- mtgp_rk4_in_acc, the
     // zero tableau entries -- which is then added: the same sums in the same order)
 #pragma unroll 1
-    for (int stage = 0; stage < n_stages; ++stage) {
+    for (int stage = stage0; stage < n_stages; ++stage) {
       float xt[NV], at[NA], y[NV];
-      stage_in_n<NV>(stage, x, kx, ax, dt, xt);
-      stage_in_n<NA>(stage, a, ka, aa, dt, at);
+      rk.template in<NV>(stage, x, kx, ax, dt, xt);
+      rk.template in<NA>(stage, a, ka, aa, dt, at);
       if (stage > 0) {
-        stage_acc_n<NV>(stage - 1, ax, kx);
-        stage_acc_n<NA>(stage - 1, aa, ka);
+        rk.template acc<NV>(stage - 1, ax, kx);
+        rk.template acc<NA>(stage - 1, aa, ka);
       }
 #pragma unroll
       for (int j = 0; j < NA; ++j)
@@ -1845,8 +2037,8 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((NA > 
       else run_role<JIT, 1>(A, Ln, ng, 0, A.m.prog_readout, D, ur);
       const float u = ur[0];
       env.drift(xt, u, kx);
-      // stages 1 and 2 share the time t + dt/2, hence the noise draw
-      if (NOISE && stage != 2) obs_noise_vec<NV>(nzc, stage_time(stage, t, dt), nzv);
+      // RK4's stages 1 and 2 share the time t + dt/2, hence the noise draw
+      if (NOISE && rk.draws(stage)) obs_noise_vec<NV>(nzc, rk.time(stage, t, dt), nzv);
       ctl_obs_apply<Env>(xt, nzv, y);
 #pragma unroll
       for (int i = 0; i < NV; ++i) D.put(i, y[i]);
@@ -1860,8 +2052,8 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((NA > 
         for (int j = 0; j < NA; ++j) fa0[j] = ka[j];
       }
     }
-    stage_acc_n<NV>(n_stages - 1, ax, kx);
-    stage_acc_n<NA>(n_stages - 1, aa, ka);
+    rk.template finish<NV>(ax, kx);
+    rk.template finish<NA>(aa, ka);
     float x1[NV], a1[NA];
 #pragma unroll
     for (int i = 0; i < NV; ++i) x1[i] = euler ? x[i] + fx0[i] * dt : mtgp_rk4_out(x[i], ax[i], dt);
@@ -1898,6 +2090,8 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((NA > 
       if (MTGP_DEAD_ZERO) {            // nothing reads this lane's state again (dead_state_clear)
         dead_state_clear<NV>(x);
         dead_state_clear<NA>(a);
+        rk.template dead_clear<NV>(kx);
+        rk.template dead_clear<NA>(ka);
       }
     }
     clk.advance();
@@ -1989,6 +2183,8 @@ __device__ __forceinline__ void ctl_static_jit(const KArgs& A, const Lane& Ln) {
   const bool fair_on = uni(A.fair) != 0;
   FairShare fair;
   if (fair_on) fair.init(A);
+  MtgpErk2 T{};  // the two-stage family's tableau (wave-uniform; NST = kSchErk2 only)
+  if constexpr (NST == kSchErk2) T = cs_erk2_tableau(A.m.solver);
   while (clk.live()) {
     if (fair_on) fair.step(Ln.lane, (uint32_t)clk.steps);
     const float t = clk.t, dt = clk.dt();
@@ -1997,10 +2193,10 @@ __device__ __forceinline__ void ctl_static_jit(const KArgs& A, const Lane& Ln) {
     auto stage = [&](auto st_c) {
       constexpr int ST = decltype(st_c)::value;
       float xt[NV], y[NV];
-      rk_in<NV>(ST, x, kx, ax, dt, xt);
-      if (NST == 4 && ST > 0) rk_acc<NV>(ST - 1, ax, kx);
-      if (NOISE && ST != 2) {
-        const float tc = ST == 0 ? t : mtgp_rk4_time(ST, t, dt);
+      cs_in<NST, NV>(ST, T, x, kx, ax, dt, xt);
+      if (NST != 1 && ST > 0) cs_acc<NST, NV>(ST - 1, T, ax, kx);
+      if (NOISE && (NST != 4 || ST != 2)) {
+        const float tc = cs_time<NST>(ST, T, t, dt);
         obs_noise_vec<NV>(nzc, tc, nzv);
         nzt = __float_as_uint(tc);
       }
@@ -2014,12 +2210,28 @@ __device__ __forceinline__ void ctl_static_jit(const KArgs& A, const Lane& Ln) {
         for (int i = 0; i < NV; ++i) fx0[i] = kx[i];
       }
     };
-    stage(std::integral_constant<int, 0>{});
+    if constexpr (NST == kSchBosh3) {  // FSAL: after the first step f0 is the last step's f3 (still in kx)
+      if (uni(clk.steps) == 0) {
+        stage(std::integral_constant<int, 0>{});
+      } else {
+#pragma unroll
+        for (int i = 0; i < NV; ++i) fx0[i] = kx[i];
+      }
+      stage(std::integral_constant<int, 1>{});
+      stage(std::integral_constant<int, 2>{});
+      stage(std::integral_constant<int, 3>{});  // its input is the step's end state: no term for f3
+    } else {
+      stage(std::integral_constant<int, 0>{});
+    }
     if constexpr (NST == 4) {
       stage(std::integral_constant<int, 1>{});
       stage(std::integral_constant<int, 2>{});
       stage(std::integral_constant<int, 3>{});
       rk_acc<NV>(3, ax, kx);
+    }
+    if constexpr (NST == kSchErk2) {
+      stage(std::integral_constant<int, 1>{});
+      cs_acc<NST, NV>(1, T, ax, kx);
     }
     float x1[NV];
 #pragma unroll
@@ -2049,7 +2261,10 @@ __device__ __forceinline__ void ctl_static_jit(const KArgs& A, const Lane& Ln) {
     if (ev) {
       dead = true;
       if (k < S) Env::fit_kill(fit);
-      if (MTGP_DEAD_ZERO) dead_state_clear<NV>(x);
+      if (MTGP_DEAD_ZERO) {
+        dead_state_clear<NV>(x);
+        if constexpr (NST == kSchBosh3) dead_state_clear<NV>(kx);  // (the reused f3 is the non-finite end state's)
+      }
     }
     clk.advance();
     if (!TRAJ && wave_all(fit.settled || dead)) break;
@@ -2069,7 +2284,7 @@ __device__ __forceinline__ void ctl_static_jit(const KArgs& A, const Lane& Ln) {
 // --------------------------------------------------------------------------------------
 // Static policy (feedforward_evaluate.py:64-110) on environment Env.  Data slots:
 // y 0..NV-1 | targets.
-template <class Env, bool TRAJ, bool NOISE, bool JIT>
+template <class Env, bool ERK, bool TRAJ, bool NOISE, bool JIT>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) k_ctl_static(KArgs A) {
   constexpr int NV = Env::NV;
   __shared__ float lds[kWavesPerBlock][kLdsWaveWords];
@@ -2078,8 +2293,13 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) k
   if (JIT) asm volatile("s_icache_inv");  // the JIT code was written by an earlier kernel
   if constexpr (JIT && !Env::kMask) {
     if (__builtin_expect(Ln.jok, 1)) {  // usable code: the JIT-only loop
+      if constexpr (ERK) {
+        if (A.m.solver == MTGP_SOLVER_BOSH3) ctl_static_jit<Env, TRAJ, NOISE, kSchBosh3>(A, Ln);
+        else ctl_static_jit<Env, TRAJ, NOISE, kSchErk2>(A, Ln);
+      } else {
       if (A.m.solver == MTGP_SOLVER_EULER) ctl_static_jit<Env, TRAJ, NOISE, 1>(A, Ln);
       else ctl_static_jit<Env, TRAJ, NOISE, 4>(A, Ln);
+      }
       return;
     }
   }
@@ -2139,23 +2359,30 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) k
     }
   };
 
-  const bool euler = A.m.solver == MTGP_SOLVER_EULER;  // diffrax.Euler: one stage, y + f dt
-  const int n_stages = euler ? 1 : 4;
   CsClock clk;
   clk.init(A);
   int k = 0;
   if (MTGP_DEAD_ZERO && dead) dead_state_clear<NV>(x);  // an inactive lane: as a lane whose solve has ended
+  CsRolled<ERK> rk;  // Euler / RK4, or (ERK) the two-stage family and Bosh3
+  rk.init(A.m.solver);
+  const bool euler = rk.euler;
+  const int n_stages = rk.n_stages;
   while (clk.live()) {
     const float t = clk.t, dt = clk.dt();
+    const int stage0 = rk.first_stage(clk.steps);
+    if (stage0 != 0) {  // Bosh3 after the first step: f0 is the last step's f3 (still in kx)
+#pragma unroll
+      for (int i = 0; i < NV; ++i) fx0[i] = kx[i];
+    }
     // (the stage input reads the b-weighted sum before f_{stage-1}'s term -- mtgp_rk4_in_acc, the
     // zero tableau entries -- which is then added: the same sums in the same order)
 #pragma unroll 1
-    for (int stage = 0; stage < n_stages; ++stage) {
+    for (int stage = stage0; stage < n_stages; ++stage) {
       float xt[NV], y[NV];
-      stage_in_n<NV>(stage, x, kx, ax, dt, xt);
-      if (stage > 0) stage_acc_n<NV>(stage - 1, ax, kx);
-      // stages 1 and 2 share the time t + dt/2, hence the noise draw
-      if (NOISE && stage != 2) obs_noise_vec<NV>(nzc, stage_time(stage, t, dt), nzv);
+      rk.template in<NV>(stage, x, kx, ax, dt, xt);
+      if (stage > 0) rk.template acc<NV>(stage - 1, ax, kx);
+      // RK4's stages 1 and 2 share the time t + dt/2, hence the noise draw
+      if (NOISE && rk.draws(stage)) obs_noise_vec<NV>(nzc, rk.time(stage, t, dt), nzv);
       ctl_obs_apply<Env>(xt, nzv, y);
 #pragma unroll
       for (int i = 0; i < NV; ++i) D.put(i, y[i]);
@@ -2167,7 +2394,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) k
         for (int i = 0; i < NV; ++i) fx0[i] = kx[i];
       }
     }
-    stage_acc_n<NV>(n_stages - 1, ax, kx);
+    rk.template finish<NV>(ax, kx);
     float x1[NV];
 #pragma unroll
     for (int i = 0; i < NV; ++i) x1[i] = euler ? x[i] + fx0[i] * dt : mtgp_rk4_out(x[i], ax[i], dt);
@@ -2191,7 +2418,10 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) k
     if (ev) {
       dead = true;
       if (k < S) Env::fit_kill(fit);
-      if (MTGP_DEAD_ZERO) dead_state_clear<NV>(x);
+      if (MTGP_DEAD_ZERO) {
+        dead_state_clear<NV>(x);
+        rk.template dead_clear<NV>(kx);
+      }
     }
     clk.advance();
     if (!TRAJ && wave_all(fit.settled || dead)) break;
@@ -2566,7 +2796,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MTGP_D
 
 // --------------------------------------------------------------------------------------
 // Symbolic regression of an ODE (SR_evaluator.py:57-94): dx_i = tree_i(x); MSE vs ys_true.
-template <int NV, bool TRAJ, bool JIT>
+template <int NV, bool TRAJ, bool JIT, bool ERK = false>
 __global__ void __launch_bounds__(256) k_sr(KArgs A) {
   __shared__ float lds[kWavesPerBlock][kLdsWaveWords];
   Lane Ln;
@@ -2614,25 +2844,32 @@ __global__ void __launch_bounds__(256) k_sr(KArgs A) {
       for (int d = 0; d < NV; ++d) store_row(A.out.xs, ((size_t)k * NV + d) * PR, loff, xs[d], PR);
     }
   };
-  const bool euler = A.m.solver == MTGP_SOLVER_EULER;  // diffrax.Euler: one stage, y + f dt
-  const int n_stages = euler ? 1 : 4;
   CsClock clk;
   clk.init(A);
   int k = 0;
   const bool fair_on = uni(A.fair) != 0;
   FairShare fair;
   if (fair_on) fair.init(A);
+  CsRolled<ERK> rk;  // Euler / RK4, or (ERK) the two-stage family and Bosh3
+  rk.init(A.m.solver);
+  const bool euler = rk.euler;
+  const int n_stages = rk.n_stages;
   while (clk.live()) {
     if (fair_on) fair.step(Ln.lane, (uint32_t)clk.steps);
     const float dt = clk.dt();
+    const int stage0 = rk.first_stage(clk.steps);
+    if (stage0 != 0) {  // Bosh3 after the first step: f0 is the last step's f3 (still in kx)
+#pragma unroll
+      for (int i = 0; i < NV; ++i) fx0[i] = kx[i];
+    }
     // (the stage input reads the b-weighted sum before f_{stage-1}'s term -- mtgp_rk4_in_acc, the
     // zero tableau entries -- which is then added: the same sums in the same order)
 #pragma unroll 1
-    for (int stage = 0; stage < n_stages; ++stage) {
+    for (int stage = stage0; stage < n_stages; ++stage) {
 #pragma unroll
       for (int i = 0; i < NV; ++i) {
-        D.put(i, stage_in(stage, x[i], kx[i], ax[i], dt));
-        if (stage > 0) ax[i] = stage_acc(stage - 1, ax[i], kx[i]);
+        D.put(i, rk.in1(stage, x[i], kx[i], ax[i], dt));
+        if (stage > 0) ax[i] = rk.acc1(stage - 1, ax[i], kx[i]);
       }
       run_role<JIT, NV>(A, Ln, ng, 0, A.m.prog_state, D, kx, A.chain_state != 0);
       if (stage == 0) {
@@ -2641,7 +2878,7 @@ __global__ void __launch_bounds__(256) k_sr(KArgs A) {
       }
     }
 #pragma unroll
-    for (int i = 0; i < NV; ++i) ax[i] = stage_acc(n_stages - 1, ax[i], kx[i]);
+    for (int i = 0; i < NV; ++i) ax[i] = rk.finish1(ax[i], kx[i]);
     float x1[NV];
 #pragma unroll
     for (int i = 0; i < NV; ++i) x1[i] = euler ? x[i] + fx0[i] * dt : mtgp_rk4_out(x[i], ax[i], dt);
@@ -2890,7 +3127,7 @@ __device__ __forceinline__ uint32_t lds_address(const float* p) {
 // The per-save MSE (components summed in index order, sr.py:24) is needed by wave 0 only, which
 // writes the fitness; the other waves skip the 64 LDS reads (every wave summing measured 0.7 %
 // slower at C5, profiles/r03/v10_ab_noprog_mse.log).
-template <bool TRAJ, bool JIT>
+template <bool TRAJ, bool JIT, bool ERK = false>
 __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) k_sr_wide(KArgs A) {
   extern __shared__ float wl[];
   Lane Ln;
@@ -2965,17 +3202,30 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) k
     }
     __syncthreads();
   };
-  const bool euler = A.m.solver == MTGP_SOLVER_EULER;  // diffrax.Euler: one stage, y + f dt
-  const int n_stages = euler ? 1 : 4;
   CsClock clk;
   clk.init(A);
   int k = 0;
+  CsRolled<ERK> rk;  // Euler / RK4, or (ERK) the two-stage family and Bosh3
+  rk.init(A.m.solver);
+  const bool euler = rk.euler;
+  const int n_stages = rk.n_stages;
   while (clk.live()) {  // (no FairShare: the workgroup's waves meet at a barrier every stage)
     const float dt = clk.dt();
+    // Bosh3 after the first step: f0 is the last step's f3 (kept in fx0 at that step's end), so this
+    // wave's components' stage-1 inputs replace the stage-0 inputs in cur
+    const int stage0 = rk.first_stage(clk.steps);
+    if (stage0 != 0) {
+#pragma unroll
+      for (int t = 0; t < kWideComp; ++t) {
+        if (c0 + t < NV) cur[(c0 + t) * kWave] = rk.in1(1, x[t], fx0[t], ax[t], dt);
+        ax[t] = rk.acc1(0, ax[t], fx0[t]);
+      }
+      __syncthreads();  // (every wave is past the last step's barrier and reads cur only after this one)
+    }
     // (the next stage's input reads the b-weighted sum before this stage's term -- mtgp_rk4_in_acc,
     // the zero tableau entries -- which is then added: the same sums in the same order)
 #pragma unroll 1
-    for (int stage = 0; stage < n_stages; ++stage) {
+    for (int stage = stage0; stage < n_stages; ++stage) {
       // trees of this wave's components on the shared stage vector; f parks in nxt
       if (JIT && Ln.jok && A.chain_store) {  // one call: this wave's components' units, results into nxt
         const uint32_t off = (uint32_t)__builtin_amdgcn_readlane((int)Ln.jtab, A.m.prog_state + c0);
@@ -3029,8 +3279,8 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) k
         if (c < NV) {
           const float kv = nxt[c * kWave];
           if (stage == 0) fx0[t] = kv;
-          if (!last) nxt[c * kWave] = stage_in(stage + 1, x[t], kv, ax[t], dt);  // the next stage's input
-          ax[t] = stage_acc(stage, ax[t], kv);
+          if (!last) nxt[c * kWave] = rk.in1(stage + 1, x[t], kv, ax[t], dt);  // the next stage's input
+          if (rk.has_term(stage)) ax[t] = rk.acc1(stage, ax[t], kv);
         }
       }
       __syncthreads();
@@ -3062,6 +3312,11 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) k
       for (int t = 0; t < kWideComp; ++t) x[t] = x1[t];
     }
     if (ev) dead = true;
+    if (rk.first_stage(1) != 0) {  // Bosh3: this step's f3 (in cur) is the next step's f0
+#pragma unroll
+      for (int t = 0; t < kWideComp; ++t)
+        if (c0 + t < NV) fx0[t] = cur[(c0 + t) * kWave];
+    }
 #pragma unroll
     for (int t = 0; t < kWideComp; ++t)
       if (c0 + t < NV) cur[(c0 + t) * kWave] = dead ? kInf : x[t];
@@ -5090,7 +5345,8 @@ template <class Env, int NA>
 int launch_dyn(const KArgs& A, bool jit, bool noise, bool traj, dim3 grid, dim3 block, hipStream_t s) {
   // (NA > 3, state_size 4 .. kNaWide: the data vector lives in LDS -- interpreter, or LDS-data JIT
   // code, round 6)
-  return launch_timed([&] { MTGP_CTL_VARIANTS(k_ctl_dynamic, Env, NA); }, s);
+  if (cs_is_erk(A.m.solver)) return launch_timed([&] { MTGP_CTL_VARIANTS(k_ctl_dynamic, Env, NA, true); }, s);
+  return launch_timed([&] { MTGP_CTL_VARIANTS(k_ctl_dynamic, Env, NA, false); }, s);
 }
 
 // Launch 2's order (round 6): the parked waves longest-first by their remaining-work estimate
@@ -5228,7 +5484,8 @@ int launch_ctl(const KArgs& A, const MtgpModel* model, const MtgpRollouts* ro, b
     if constexpr (std::is_same<Env, EnvAcrobot>::value)  // (a unit of its own: MTGP_TU 10)
       return mtgp_tu_launch_acrobot_static(&A, jit, noise, traj, grid.x, block.x, s);
     else
-      return launch_timed([&] { MTGP_CTL_VARIANTS(k_ctl_static, Env); }, s);
+      return cs_is_erk(A.m.solver) ? launch_timed([&] { MTGP_CTL_VARIANTS(k_ctl_static, Env, true); }, s)
+                                   : launch_timed([&] { MTGP_CTL_VARIANTS(k_ctl_static, Env, false); }, s);
   }
   switch (model->state_size) {
     case 1: return launch_dyn<Env, 1>(A, jit, noise, traj, grid, block, s);
@@ -5306,7 +5563,8 @@ int mtgp_tu_launch_acrobot_static(const void* Ap, bool jit, bool noise, bool tra
                                   hipStream_t s) {
   const KArgs& A = *(const KArgs*)Ap;
   const dim3 grid(grid_), block(block_);
-  return launch_timed([&] { MTGP_CTL_VARIANTS(k_ctl_static, EnvAcrobot); }, s);
+  if (cs_is_erk(A.m.solver)) return launch_timed([&] { MTGP_CTL_VARIANTS(k_ctl_static, EnvAcrobot, true); }, s);
+  return launch_timed([&] { MTGP_CTL_VARIANTS(k_ctl_static, EnvAcrobot, false); }, s);
 }
 #endif
 #if MTGP_TU_ACRO_MASK
@@ -5384,6 +5642,14 @@ int mtgp_tu_launch_sr(MTGP_TU_SR_ARGS) {
       const long v = atol(e);
       if (v > 0 && (size_t)v > lds && v <= 160 * 1024) lds = (size_t)v;
     }
+    if (cs_is_erk(model->solver))  // the two-stage family and Bosh3: kernels of their own
+      return launch_timed([&] {
+        if (jit) {
+          if (traj) hipLaunchKernelGGL((k_sr_wide<true, true, true>), wgrid, wblock, lds, s, A);
+          else hipLaunchKernelGGL((k_sr_wide<false, true, true>), wgrid, wblock, lds, s, A);
+        } else if (traj) hipLaunchKernelGGL((k_sr_wide<true, false, true>), wgrid, wblock, lds, s, A);
+        else hipLaunchKernelGGL((k_sr_wide<false, false, true>), wgrid, wblock, lds, s, A);
+      }, s);
     return launch_timed([&] {
       if (jit) {
         if (traj) hipLaunchKernelGGL((k_sr_wide<true, true>), wgrid, wblock, lds, s, A);
@@ -5401,12 +5667,19 @@ int mtgp_tu_launch_sr(MTGP_TU_SR_ARGS) {
         else hipLaunchKernelGGL((k_sr_dopri5<NV, false, true>), grid, block, 0, s, A);                  \
       } else if (traj) hipLaunchKernelGGL((k_sr_dopri5<NV, true, false>), grid, block, 0, s, A);        \
       else hipLaunchKernelGGL((k_sr_dopri5<NV, false, false>), grid, block, 0, s, A);                   \
+    } else if (erk) {                                                                                   \
+      if (jit) {                                                                                        \
+        if (traj) hipLaunchKernelGGL((k_sr<NV, true, true, true>), grid, block, 0, s, A);               \
+        else hipLaunchKernelGGL((k_sr<NV, false, true, true>), grid, block, 0, s, A);                   \
+      } else if (traj) hipLaunchKernelGGL((k_sr<NV, true, false, true>), grid, block, 0, s, A);         \
+      else hipLaunchKernelGGL((k_sr<NV, false, false, true>), grid, block, 0, s, A);                    \
     } else if (jit) {                                                                                   \
       if (traj) hipLaunchKernelGGL((k_sr<NV, true, true>), grid, block, 0, s, A);                       \
       else hipLaunchKernelGGL((k_sr<NV, false, true>), grid, block, 0, s, A);                           \
     } else if (traj) hipLaunchKernelGGL((k_sr<NV, true, false>), grid, block, 0, s, A);                 \
     else hipLaunchKernelGGL((k_sr<NV, false, false>), grid, block, 0, s, A);                            \
   }, s);
+  const bool erk = cs_is_erk(model->solver);  // the two-stage family and Bosh3: kernels of their own
   switch (model->n_var) {
     MTGP_SR(1)
     MTGP_SR(2)
@@ -5864,7 +6137,9 @@ int mtgp_eval_rk4_jit(const MtgpModel* model, const MtgpInstr* prog, const int32
   if ((int64_t)P * Rp > INT32_MAX) return MTGP_ERR_ARG;  // lane offsets are 32-bit
   if ((int64_t)P * n_prog * L * (int64_t)sizeof(MtgpInstr) > UINT32_MAX) return MTGP_ERR_ARG;  // 32-bit program offsets
   const bool dopri5 = model->solver == MTGP_SOLVER_DOPRI5;
-  if (model->solver != MTGP_SOLVER_RK4 && model->solver != MTGP_SOLVER_EULER && !dopri5) return MTGP_ERR_ARG;
+  // fixed step: RK4, Euler and (ABI v24) Heun, Midpoint, Ralston, Bosh3
+  const bool erk = model->solver >= MTGP_SOLVER_HEUN && model->solver <= MTGP_SOLVER_BOSH3;
+  if (model->solver != MTGP_SOLVER_RK4 && model->solver != MTGP_SOLVER_EULER && !dopri5 && !erk) return MTGP_ERR_ARG;
   if (dopri5) {  // adaptive: save points come from ts, steps from the controller
     if (model->model == MTGP_MODEL_SR && (model->n_var < 1 || model->n_var > MTGP_MAX_DATA)) return MTGP_ERR_ARG;
     if (model->n_save < 2 || model->max_steps <= 0 || !(model->h > 0.0f)) return MTGP_ERR_ARG;

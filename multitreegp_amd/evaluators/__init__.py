@@ -10,7 +10,9 @@ one launch; these per-candidate calls exist for API parity and trajectory inspec
 Solver: BASELINE.json prescribes an explicit fixed-step RK4 (``RK4()`` or "rk4" with
 ``ConstantStepSize()``); omitting ``solver`` gives the reference's default ``Euler()`` (fixed
 step).  Both follow diffrax.ConstantStepSize exactly (include/mtgp_cstep.h): accumulated f32 step
-ends, per-step dt, SaveAt(ts) for any non-decreasing ts through the dense output.  The notebooks' adaptive ``Dopri5()`` + ``PIDController(rtol, atol, dtmin)`` (SURVEY.md
+ends, per-step dt, SaveAt(ts) for any non-decreasing ts through the dense output; so do ``Heun()``,
+``Midpoint()``, ``Ralston()`` and ``Bosh3()`` (evaluation only: no PID controller, no coefficient
+optimisation).  The notebooks' adaptive ``Dopri5()`` + ``PIDController(rtol, atol, dtmin)`` (SURVEY.md
 §8f row 2, spec include/mtgp_dopri5.h) runs on the GPU for the dynamic and static control
 evaluators (every environment) and for ``SREvaluator``.
 """
@@ -40,6 +42,43 @@ class Euler:
 
     def __repr__(self):
         return "Euler()"
+
+
+class Heun:
+    """Heun's method, fixed step dt0 (diffrax.Heun + ConstantStepSize): two stages, order 2,
+    c = 1, b = (1/2, 1/2); cubic Hermite dense output (include/mtgp_cstep.h)."""
+    name = "Heun"
+
+    def __repr__(self):
+        return "Heun()"
+
+
+class Midpoint:
+    """Explicit midpoint method, fixed step dt0 (diffrax.Midpoint + ConstantStepSize): two stages,
+    order 2, c = 1/2, b = (0, 1)."""
+    name = "Midpoint"
+
+    def __repr__(self):
+        return "Midpoint()"
+
+
+class Ralston:
+    """Ralston's method, fixed step dt0 (diffrax.Ralston + ConstantStepSize): two stages, order 2,
+    c = 3/4, b = (1/3, 2/3)."""
+    name = "Ralston"
+
+    def __repr__(self):
+        return "Ralston()"
+
+
+class Bosh3:
+    """Bogacki-Shampine 3(2), fixed step dt0 (diffrax.Bosh3 + ConstantStepSize): order 3, three
+    right-hand-side evaluations per step (FSAL: a step's last derivative is the next step's first).
+    Adaptive use (a PIDController) is not implemented."""
+    name = "Bosh3"
+
+    def __repr__(self):
+        return "Bosh3()"
 
 
 class ConstantStepSize:
@@ -98,8 +137,8 @@ class PIDController:
 
 
 def _check_solver(solver, controller, adaptive_ok: bool = False) -> str:
-    """-> "rk4", "euler" or "dopri5" (the latter needs a PIDController and an evaluator that
-    supports it)."""
+    """-> "rk4", "euler", "heun", "midpoint", "ralston", "bosh3" (fixed step: no controller or
+    ConstantStepSize) or "dopri5" (needs a PIDController and an evaluator that supports it)."""
     sname = solver.lower() if isinstance(solver, str) else getattr(solver, "name", type(solver).__name__)
     sname = str(sname).lower()
     cname = None if controller is None else getattr(controller, "name", type(controller).__name__)
@@ -109,9 +148,9 @@ def _check_solver(solver, controller, adaptive_ok: bool = False) -> str:
         if cname != "PIDController":
             raise NotImplementedError("Dopri5 needs a PIDController (fixed-step Dopri5 is not implemented)")
         return "dopri5"
-    if sname not in ("rk4", "euler"):
-        raise NotImplementedError(f"solver {solver!r}: implemented solvers are Euler and RK4 (fixed step) and "
-                                  "Dopri5 (PID)")
+    if sname not in _FIXED_STEP_CODES:
+        raise NotImplementedError(f"solver {solver!r}: implemented solvers are Euler, Heun, Midpoint, Ralston, "
+                                  "Bosh3 and RK4 (fixed step) and Dopri5 (PID)")
     if cname is not None and cname != "ConstantStepSize":
         raise NotImplementedError(f"stepsize_controller {controller!r}: {sname} runs with ConstantStepSize only")
     return sname
@@ -126,9 +165,14 @@ def _check_max_steps(max_steps) -> int:
     return int(max_steps)
 
 
+# the fixed-step solver kinds and their MTGP_SOLVER_* codes
+_FIXED_STEP_CODES = {"rk4": nat.SOLVER_RK4, "euler": nat.SOLVER_EULER, "heun": nat.SOLVER_HEUN,
+                     "midpoint": nat.SOLVER_MIDPOINT, "ralston": nat.SOLVER_RALSTON, "bosh3": nat.SOLVER_BOSH3}
+
+
 def _solver_fields(kind: str, controller, max_steps: int) -> dict:
     if kind != "dopri5":  # ConstantStepSize: max_steps bounds the fixed-step solve too (ABI v18)
-        return dict(solver=nat.SOLVER_EULER if kind == "euler" else nat.SOLVER_RK4, max_steps=int(max_steps), rtol=0.0,
+        return dict(solver=_FIXED_STEP_CODES[kind], max_steps=int(max_steps), rtol=0.0,
                     atol=0.0, dtmin=0.0, dtmax=0.0)
     return dict(solver=nat.SOLVER_DOPRI5, max_steps=int(max_steps), rtol=controller.rtol, atol=controller.atol,
                 dtmin=controller.dtmin or 0.0, dtmax=controller.dtmax or 0.0, **controller.model_fields())
@@ -490,5 +534,5 @@ class SREvaluator(_CandidateAPI):
         return specs, roles
 
 
-__all__ = ["RK4", "Euler", "ConstantStepSize", "Dopri5", "PIDController", "DynamicEvaluator", "FeedforwardEvaluator", "SREvaluator",
+__all__ = ["RK4", "Euler", "Heun", "Midpoint", "Ralston", "Bosh3", "ConstantStepSize", "Dopri5", "PIDController", "DynamicEvaluator", "FeedforwardEvaluator", "SREvaluator",
            "fixed_schedule", "rk4_schedule", "constant_step_grid", "adaptive_schedule", "acrobot_mask"]
