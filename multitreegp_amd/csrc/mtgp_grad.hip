@@ -22,6 +22,7 @@
 #include "mtgp_dopri5.h"
 #include "mtgp_cstep.h"
 #include "mtgp_jit_dual.h"
+#include "mtgp_variants.h"
 
 namespace {
 
@@ -1780,6 +1781,13 @@ static bool grad_args(GradArgs& A, const MtgpModel* model, const MtgpInstr* prog
   return true;
 }
 
+// the kernels' ENV template argument from MtgpModel.env (checked by the caller to be one of the three)
+template <class F>
+static decltype(auto) env_variant(int env, F&& f) {
+  return mtgp::int_variant<MTGP_ENV_ACROBOT, MTGP_ENV_HARMONIC_OSCILLATOR, MTGP_ENV_STIRRED_TANK_REACTOR>(
+      env, std::forward<F>(f));
+}
+
 // Launch k_ctl_grad_wide<ENV, DP> with the dynamic LDS of the actual state and data sizes.  Both
 // forms can pass the 64 KB a kernel gets by default, so each instantiation raises its limit to its
 // ceiling (ND = 20, D = kWideData) once per device, not per launch.
@@ -1844,32 +1852,25 @@ extern "C" int mtgp_ctl_grad_jit(const MtgpModel* model, const MtgpInstr* prog, 
   if (wide) {
     const int nd = nv + na;
     const dim3 wgrid((unsigned)(lanes / kWideBlock));
-    int rc;
-    if (model->env == MTGP_ENV_ACROBOT) rc = dopri5 ? wide_launch<0, true>(A, wgrid, nd, D, s) : wide_launch<0, false>(A, wgrid, nd, D, s);
-    else if (model->env == MTGP_ENV_HARMONIC_OSCILLATOR)
-      rc = dopri5 ? wide_launch<1, true>(A, wgrid, nd, D, s) : wide_launch<1, false>(A, wgrid, nd, D, s);
-    else rc = dopri5 ? wide_launch<2, true>(A, wgrid, nd, D, s) : wide_launch<2, false>(A, wgrid, nd, D, s);
+    const int rc = env_variant(model->env, [&](auto E) {
+      constexpr int kEnv = E();
+      return mtgp::with_flag(dopri5, [&](auto DP) { return wide_launch<kEnv, DP()>(A, wgrid, nd, D, s); });
+    });
     if (rc != MTGP_OK) return rc;
     hipLaunchKernelGGL(k_grad_reduce, dim3((unsigned)(((long)P * K + 255) / 256)), dim3(256), 0, s, A);
     if (hipGetLastError() != hipSuccess) return MTGP_ERR_LAUNCH;
     return MTGP_OK;
   }
   const dim3 grid((unsigned)((lanes + 255) / 256)), block(256);
-#define MTGP_CG2(E, DPV)                                                                 \
-  switch (na) {                                                                           \
-    case 0: hipLaunchKernelGGL((k_ctl_grad<E, 0, DPV>), grid, block, 0, s, A); break;     \
-    case 1: hipLaunchKernelGGL((k_ctl_grad<E, 1, DPV>), grid, block, 0, s, A); break;     \
-    case 2: hipLaunchKernelGGL((k_ctl_grad<E, 2, DPV>), grid, block, 0, s, A); break;     \
-    default: hipLaunchKernelGGL((k_ctl_grad<E, 3, DPV>), grid, block, 0, s, A); break;    \
-  }
-#define MTGP_CG(E)              \
-  if (dopri5) MTGP_CG2(E, true) \
-  else MTGP_CG2(E, false)
-  if (model->env == MTGP_ENV_ACROBOT) { MTGP_CG(0) }
-  else if (model->env == MTGP_ENV_HARMONIC_OSCILLATOR) { MTGP_CG(1) }
-  else { MTGP_CG(2) }
-#undef MTGP_CG
-#undef MTGP_CG2
+  env_variant(model->env, [&](auto E) {
+    constexpr int kEnv = E();
+    mtgp::int_variant<0, 1, 2, 3>(na, [&](auto NA) {  // (na <= 3 here)
+      constexpr int kNa = NA();
+      mtgp::with_flag(dopri5, [&](auto DP) {
+        hipLaunchKernelGGL((k_ctl_grad<kEnv, kNa, DP()>), grid, block, 0, s, A);
+      });
+    });
+  });
   if (hipGetLastError() != hipSuccess) return MTGP_ERR_LAUNCH;
   hipLaunchKernelGGL(k_grad_reduce, dim3((unsigned)(((long)P * K + 255) / 256)), dim3(256), 0, s, A);
   if (hipGetLastError() != hipSuccess) return MTGP_ERR_LAUNCH;

@@ -34,6 +34,7 @@
 #include "mtgp_flatten.h"
 #include "mtgp_flatten_uniform.h"
 #include "mtgp_jit.h"
+#include "mtgp_variants.h"
 
 // Translation units.  The library is compiled from this file several times in parallel
 // (__graft_entry__.build_hip): MTGP_TU=0 holds the C ABI, the Acrobot / SR / JIT / flatten /
@@ -46,31 +47,22 @@
 // fixed-step Acrobot kernels of the static policy (the C2 hot kernel; out of unit 7 since round 8,
 // which compiles unit 7 without the SLP vectorizer -- that costs the static loop 3 %), behind one
 // hidden C++ entry each.  Without MTGP_TU it is one monolithic TU.
-#ifndef MTGP_TU
-#define MTGP_TU_MAIN 1
-#define MTGP_TU_HARMONIC 1
-#define MTGP_TU_REACTOR 1
-#define MTGP_TU_ACRO_DOPRI5 1
-#define MTGP_TU_HARMONIC_DOPRI5 1
-#define MTGP_TU_REACTOR_DOPRI5 1
-#define MTGP_TU_ACRO_MASK 1
-#define MTGP_TU_ACRO 1
-#define MTGP_TU_SR 1
-#define MTGP_TU_DP_RT 1
-#define MTGP_TU_ACRO_STATIC 1
+#ifdef MTGP_TU
+#define MTGP_TU_IS(n) (MTGP_TU == (n))
 #else
-#define MTGP_TU_MAIN (MTGP_TU == 0)
-#define MTGP_TU_HARMONIC (MTGP_TU == 1)
-#define MTGP_TU_REACTOR (MTGP_TU == 2)
-#define MTGP_TU_ACRO_DOPRI5 (MTGP_TU == 3)
-#define MTGP_TU_HARMONIC_DOPRI5 (MTGP_TU == 4)
-#define MTGP_TU_REACTOR_DOPRI5 (MTGP_TU == 5)
-#define MTGP_TU_ACRO_MASK (MTGP_TU == 6)
-#define MTGP_TU_ACRO (MTGP_TU == 7)
-#define MTGP_TU_SR (MTGP_TU == 8)
-#define MTGP_TU_DP_RT (MTGP_TU == 9)
-#define MTGP_TU_ACRO_STATIC (MTGP_TU == 10)
+#define MTGP_TU_IS(n) 1
 #endif
+#define MTGP_TU_MAIN MTGP_TU_IS(0)
+#define MTGP_TU_HARMONIC MTGP_TU_IS(1)
+#define MTGP_TU_REACTOR MTGP_TU_IS(2)
+#define MTGP_TU_ACRO_DOPRI5 MTGP_TU_IS(3)
+#define MTGP_TU_HARMONIC_DOPRI5 MTGP_TU_IS(4)
+#define MTGP_TU_REACTOR_DOPRI5 MTGP_TU_IS(5)
+#define MTGP_TU_ACRO_MASK MTGP_TU_IS(6)
+#define MTGP_TU_ACRO MTGP_TU_IS(7)
+#define MTGP_TU_SR MTGP_TU_IS(8)
+#define MTGP_TU_DP_RT MTGP_TU_IS(9)
+#define MTGP_TU_ACRO_STATIC MTGP_TU_IS(10)
 
 namespace {
 
@@ -5266,87 +5258,53 @@ hsa_status_t jit_find_pool(hsa_amd_memory_pool_t p, void* data) {
 
 #endif  // MTGP_TU_MAIN
 
-// Kernel timing (mtgp_set_timing / mtgp_last_kernel_ms / mtgp_kernel_ms_history): the switch is
-// process-wide; the event pairs (a ring of the last kTimingRing launches, so a caller can read the
-// durations of a whole run after one synchronisation instead of stalling the queue every launch)
-// are per host thread and re-created when the thread moves to another device, so concurrent callers
-// on different threads / streams / devices never share events.
-std::atomic<bool> g_timing{false};
-constexpr int kTimingRing = 1024;
-struct TimingState {
-  hipEvent_t ev0[kTimingRing] = {}, ev1[kTimingRing] = {};
-  int device = -1;
-  long long count = 0;  // timed launches recorded on `device`
-  void reset(int dev) {
-    for (int i = 0; i < kTimingRing; ++i)
-      if (ev0[i]) { (void)hipEventDestroy(ev0[i]); (void)hipEventDestroy(ev1[i]); ev0[i] = ev1[i] = nullptr; }
-    device = dev;
-    count = 0;
-  }
-};
-thread_local TimingState t_timing;
-
-float timing_ms(const TimingState& ts, long long i) {
-  const int k = (int)(i % kTimingRing);
-  float ms = -1.0f;
-  (void)hipEventElapsedTime(&ms, ts.ev0[k], ts.ev1[k]);
-  return ms;
-}
-
+// One launch step of a unit: run `launch` (kernel launches), then the launch status as an ABI code.
+// Nothing is timed here: the unit that holds the C ABI times a whole evaluator call (launch_timed).
 template <class F>
-int launch_timed(F&& launch, hipStream_t s) {
-  const bool timing = g_timing.load(std::memory_order_relaxed);
-  TimingState& ts = t_timing;
-  int k = 0;
-  if (timing) {
-    int dev = -1;
-    (void)hipGetDevice(&dev);
-    if (ts.device != dev) ts.reset(dev);
-    k = (int)(ts.count % kTimingRing);
-    if (!ts.ev0[k]) { (void)hipEventCreate(&ts.ev0[k]); (void)hipEventCreate(&ts.ev1[k]); }
-    (void)hipEventRecord(ts.ev0[k], s);
-  }
+int launch_checked(F&& launch) {
   launch();
-  if (hipGetLastError() != hipSuccess) return MTGP_ERR_LAUNCH;
-  if (timing) { (void)hipEventRecord(ts.ev1[k], s); ++ts.count; }
-  return MTGP_OK;
+  return hipGetLastError() == hipSuccess ? MTGP_OK : MTGP_ERR_LAUNCH;
 }
 
 }  // namespace
 
-// the eight (TRAJ, NOISE, JIT) variants of one control kernel; an Env with kMask (EnvAcrobotMask)
-// has the four TRAJ variants only (the caller passes traj = true)
-template <class E, int... N>
-constexpr bool kTrajOnly = E::kMask;
-#define MTGP_CTL_VARIANTS(KERNEL, ...)                                                                   \
-  do {                                                                                                  \
-    if (jit) {                                                                                          \
-      if (noise) {                                                                                      \
-        if (traj) hipLaunchKernelGGL((KERNEL<__VA_ARGS__, true, true, true>), grid, block, 0, s, A);    \
-        else if constexpr (!kTrajOnly<__VA_ARGS__>)                                                     \
-          hipLaunchKernelGGL((KERNEL<__VA_ARGS__, false, true, true>), grid, block, 0, s, A);           \
-      } else {                                                                                          \
-        if (traj) hipLaunchKernelGGL((KERNEL<__VA_ARGS__, true, false, true>), grid, block, 0, s, A);   \
-        else if constexpr (!kTrajOnly<__VA_ARGS__>)                                                     \
-          hipLaunchKernelGGL((KERNEL<__VA_ARGS__, false, false, true>), grid, block, 0, s, A);          \
-      }                                                                                                 \
-    } else if (noise) {                                                                                 \
-      if (traj) hipLaunchKernelGGL((KERNEL<__VA_ARGS__, true, true, false>), grid, block, 0, s, A);     \
-      else if constexpr (!kTrajOnly<__VA_ARGS__>)                                                       \
-        hipLaunchKernelGGL((KERNEL<__VA_ARGS__, false, true, false>), grid, block, 0, s, A);            \
-    } else {                                                                                            \
-      if (traj) hipLaunchKernelGGL((KERNEL<__VA_ARGS__, true, false, false>), grid, block, 0, s, A);    \
-      else if constexpr (!kTrajOnly<__VA_ARGS__>)                                                       \
-        hipLaunchKernelGGL((KERNEL<__VA_ARGS__, false, false, false>), grid, block, 0, s, A);           \
-    }                                                                                                   \
-  } while (0)
+// What a unit's entry needs to launch besides its kernel arguments: the run-time flags that pick
+// the kernel variant (mtgp_variants.h) and the launch geometry.  One definition for every unit
+// (outside the anonymous namespace: it is part of the hidden entries' signatures).
+struct MtgpLaunchCtx {
+  bool traj, noise, jit;
+  unsigned grid, block;  // 1-D workgroup count and size of the wave-per-group kernels
+  unsigned waves;        // the launch's waves (the wide SR kernels: one workgroup per wave set)
+  hipStream_t s;
+};
+// a unit's entry: C++ linkage, hidden (not part of the C ABI)
+#define MTGP_HIDDEN __attribute__((visibility("hidden")))
 
 template <class Env, int NA>
-int launch_dyn(const KArgs& A, bool jit, bool noise, bool traj, dim3 grid, dim3 block, hipStream_t s) {
+int launch_dyn(const KArgs& A, const MtgpLaunchCtx& c) {
   // (NA > 3, state_size 4 .. kNaWide: the data vector lives in LDS -- interpreter, or LDS-data JIT
   // code, round 6)
-  if (cs_is_erk(A.m.solver)) return launch_timed([&] { MTGP_CTL_VARIANTS(k_ctl_dynamic, Env, NA, true); }, s);
-  return launch_timed([&] { MTGP_CTL_VARIANTS(k_ctl_dynamic, Env, NA, false); }, s);
+  return launch_checked([&] {
+    mtgp::with_flag(cs_is_erk(A.m.solver), [&](auto ERK) {
+      constexpr bool kErk = ERK();
+      mtgp::ctl_variant<Env::kMask>(c.traj, c.noise, c.jit, [&](auto T, auto N, auto J) {
+        hipLaunchKernelGGL((k_ctl_dynamic<Env, NA, kErk, T(), N(), J()>), c.grid, c.block, 0, c.s, A);
+      });
+    });
+  });
+}
+
+// fixed-step static policy (k_ctl_static)
+template <class Env>
+int launch_static(const KArgs& A, const MtgpLaunchCtx& c) {
+  return launch_checked([&] {
+    mtgp::with_flag(cs_is_erk(A.m.solver), [&](auto ERK) {
+      constexpr bool kErk = ERK();
+      mtgp::ctl_variant<Env::kMask>(c.traj, c.noise, c.jit, [&](auto T, auto N, auto J) {
+        hipLaunchKernelGGL((k_ctl_static<Env, kErk, T(), N(), J()>), c.grid, c.block, 0, c.s, A);
+      });
+    });
+  });
 }
 
 // Launch 2's order (round 6): the parked waves longest-first by their remaining-work estimate
@@ -5387,63 +5345,61 @@ static __global__ void __launch_bounds__(1024) k_dp_order(int32_t* pending, cons
 
 // adaptive Dopri5 at a runtime state size (NA = kNaRuntime / kNaWide): interpreter variants only;
 // the non-mask environments' kernels live in TU 9 (their register allocation dominates a build)
-__attribute__((visibility("hidden"))) int mtgp_tu_launch_dp_rt(const void* A, int env, bool wide, bool noise, bool traj,
-                                                                unsigned grid, unsigned block, hipStream_t s);
+MTGP_HIDDEN int mtgp_tu_launch_dp_rt(const void* A, int env, bool wide, const MtgpLaunchCtx& c);
 template <class Env, int NA>
-int launch_dp_rt(const KArgs& A, bool noise, bool traj, dim3 grid, dim3 block, hipStream_t s) {
-  return launch_timed([&] {
-    if (noise) {
-      if (traj) hipLaunchKernelGGL((k_ctl_dopri5<Env, NA, true, true, false>), grid, block, 0, s, A);
-      else if constexpr (!Env::kMask) hipLaunchKernelGGL((k_ctl_dopri5<Env, NA, false, true, false>), grid, block, 0, s, A);
-    } else if (traj) {
-      hipLaunchKernelGGL((k_ctl_dopri5<Env, NA, true, false, false>), grid, block, 0, s, A);
-    } else if constexpr (!Env::kMask) {
-      hipLaunchKernelGGL((k_ctl_dopri5<Env, NA, false, false, false>), grid, block, 0, s, A);
-    }
-  }, s);
+int launch_dp_rt(const KArgs& A, const MtgpLaunchCtx& c) {
+  return launch_checked([&] {
+    mtgp::ctl_interp_variant<Env::kMask>(c.traj, c.noise, [&](auto T, auto N) {
+      hipLaunchKernelGGL((k_ctl_dopri5<Env, NA, T(), N(), false>), c.grid, c.block, 0, c.s, A);
+    });
+  });
 }
 
-// adaptive Dopri5 variants (k_ctl_dopri5): static = NA 0
+// adaptive Dopri5 at a state size fixed at compile time (NA 1 .. 3; the static policy: NA 0)
+template <class Env, int NA>
+int launch_dp(const KArgs& A, const MtgpLaunchCtx& c) {
+  return launch_checked([&] {
+    mtgp::ctl_variant<Env::kMask>(c.traj, c.noise, c.jit, [&](auto T, auto N, auto J) {
+      hipLaunchKernelGGL((k_ctl_dopri5<Env, NA, T(), N(), J()>), c.grid, c.block, 0, c.s, A);
+    });
+  });
+}
+
+// adaptive Dopri5 variants (k_ctl_dopri5)
 template <class Env>
-int launch_ctl_dp(const KArgs& A, const MtgpModel* model, bool jit, bool noise, bool traj, dim3 grid, dim3 block,
-                  hipStream_t s) {
-  if (model->model == MTGP_MODEL_STATIC) return launch_timed([&] { MTGP_CTL_VARIANTS(k_ctl_dopri5, Env, 0); }, s);
+int launch_ctl_dp(const KArgs& A, const MtgpModel* model, const MtgpLaunchCtx& c) {
+  if (model->model == MTGP_MODEL_STATIC) return launch_dp<Env, 0>(A, c);
   switch (model->state_size) {
-    case 1: return launch_timed([&] { MTGP_CTL_VARIANTS(k_ctl_dopri5, Env, 1); }, s);
-    case 2: return launch_timed([&] { MTGP_CTL_VARIANTS(k_ctl_dopri5, Env, 2); }, s);
-    case 3: return launch_timed([&] { MTGP_CTL_VARIANTS(k_ctl_dopri5, Env, 3); }, s);
+    case 1: return launch_dp<Env, 1>(A, c);
+    case 2: return launch_dp<Env, 2>(A, c);
+    case 3: return launch_dp<Env, 3>(A, c);
     default:  // runtime state size (round 6): interpreter only, one launch
-      if (jit || model->state_size < 4 || model->state_size > kNaWide) return MTGP_ERR_ARG;
+      if (c.jit || model->state_size < 4 || model->state_size > kNaWide) return MTGP_ERR_ARG;
       if constexpr (Env::kMask) {  // (the cost-mask kernels stay in their own TU)
-        return model->state_size > kNaRuntime ? launch_dp_rt<Env, kNaWide>(A, noise, traj, grid, block, s)
-                                              : launch_dp_rt<Env, kNaRuntime>(A, noise, traj, grid, block, s);
+        return model->state_size > kNaRuntime ? launch_dp_rt<Env, kNaWide>(A, c) : launch_dp_rt<Env, kNaRuntime>(A, c);
       } else {
         const int env = std::is_same<Env, EnvAcrobot>::value ? 0 : std::is_same<Env, EnvHarmonic>::value ? 1 : 2;
-        return mtgp_tu_launch_dp_rt(&A, env, model->state_size > kNaRuntime, noise, traj, grid.x, block.x, s);
+        return mtgp_tu_launch_dp_rt(&A, env, model->state_size > kNaRuntime, c);
       }
   }
 }
 // every environment's Dopri5 kernels live in their own translation unit (MTGP_TU 3, 4, 5)
-#define MTGP_TU_DP_ARGS \
-  const void* A, const MtgpModel* model, bool jit, bool noise, bool traj, unsigned grid, unsigned block, hipStream_t s
-__attribute__((visibility("hidden"))) int mtgp_tu_launch_acrobot_dopri5(MTGP_TU_DP_ARGS);
-__attribute__((visibility("hidden"))) int mtgp_tu_launch_harmonic_dopri5(MTGP_TU_DP_ARGS);
-__attribute__((visibility("hidden"))) int mtgp_tu_launch_reactor_dopri5(MTGP_TU_DP_ARGS);
+MTGP_HIDDEN int mtgp_tu_launch_acrobot_dopri5(const void* A, const MtgpModel* model, const MtgpLaunchCtx& c);
+MTGP_HIDDEN int mtgp_tu_launch_harmonic_dopri5(const void* A, const MtgpModel* model, const MtgpLaunchCtx& c);
+MTGP_HIDDEN int mtgp_tu_launch_reactor_dopri5(const void* A, const MtgpModel* model, const MtgpLaunchCtx& c);
 template <class Env>
-int launch_dp_entry(MTGP_TU_DP_ARGS) {
-  if constexpr (Env::kMask) return launch_ctl_dp<Env>(*(const KArgs*)A, model, jit, noise, traj, dim3(grid), dim3(block), s);
-  else if constexpr (std::is_same<Env, EnvAcrobot>::value) return mtgp_tu_launch_acrobot_dopri5(A, model, jit, noise, traj, grid, block, s);
-  else if constexpr (std::is_same<Env, EnvHarmonic>::value) return mtgp_tu_launch_harmonic_dopri5(A, model, jit, noise, traj, grid, block, s);
-  else return mtgp_tu_launch_reactor_dopri5(A, model, jit, noise, traj, grid, block, s);
+int launch_dp_entry(const KArgs& A, const MtgpModel* model, const MtgpLaunchCtx& c) {
+  if constexpr (Env::kMask) return launch_ctl_dp<Env>(A, model, c);
+  else if constexpr (std::is_same<Env, EnvAcrobot>::value) return mtgp_tu_launch_acrobot_dopri5(&A, model, c);
+  else if constexpr (std::is_same<Env, EnvHarmonic>::value) return mtgp_tu_launch_harmonic_dopri5(&A, model, c);
+  else return mtgp_tu_launch_reactor_dopri5(&A, model, c);
 }
 
 // the fixed-step static-policy Acrobot kernels' unit (MTGP_TU 10)
-__attribute__((visibility("hidden"))) int mtgp_tu_launch_acrobot_static(const void* A, bool jit, bool noise, bool traj,
-                                                                         unsigned grid, unsigned block, hipStream_t s);
+MTGP_HIDDEN int mtgp_tu_launch_acrobot_static(const void* A, const MtgpLaunchCtx& c);
 // dynamic / static evaluator on environment Env: shape checks, then the kernel variant
 template <class Env>
-int launch_ctl(const KArgs& A, const MtgpModel* model, const MtgpRollouts* ro, bool jit, bool noise, bool traj,
-               dim3 grid, dim3 block, hipStream_t s) {
+int launch_ctl(const KArgs& A, const MtgpModel* model, const MtgpRollouts* ro, const MtgpLaunchCtx& c) {
   constexpr int NV = Env::NV;
   if (model->n_var != NV || model->n_obs < 1 || model->n_obs > NV || model->n_control != 1 || !ro->params)
     return MTGP_ERR_ARG;
@@ -5455,58 +5411,49 @@ int launch_ctl(const KArgs& A, const MtgpModel* model, const MtgpRollouts* ro, b
     const int dm = model->state_size > kNaRuntime ? kDWide2 : kDWide;
     // (JIT: LDS-data code, fixed-step solvers; Dopri5: interpreter, one launch -- no parking)
     if (model->state_size > kNaWide || NV + model->state_size + 1 + model->n_targets > dm ||
-        (model->solver == MTGP_SOLVER_DOPRI5 && (jit || A.dp_budget > 0)))
+        (model->solver == MTGP_SOLVER_DOPRI5 && (c.jit || A.dp_budget > 0)))
       return MTGP_ERR_ARG;
   } else if (NV + model->state_size + 1 + model->n_targets > kDMax) {
     return MTGP_ERR_ARG;
   }
   if (model->solver == MTGP_SOLVER_DOPRI5) {
-    int rc = MTGP_OK;
-    const int lr = launch_timed([&] {
-      if (A.dp_budget <= 0) {
-        rc = launch_dp_entry<Env>(&A, model, jit, noise, traj, grid.x, block.x, s);
-        return;
-      }
-      // two launches: every wave for dp_budget attempts, then the parked waves (KArgs.dp_*)
-      if (hipMemsetAsync(A.dp_pending, 0, sizeof(int32_t), s) != hipSuccess) { rc = MTGP_ERR_LAUNCH; return; }
-      KArgs A1 = A;
-      A1.dp_pass = 1;
-      rc = launch_dp_entry<Env>(&A1, model, jit, noise, traj, grid.x, block.x, s);
-      if (rc != MTGP_OK) return;
-      hipLaunchKernelGGL(k_dp_order, dim3(1), dim3(1024), 0, s, A.dp_pending, (const float*)A.dp_state, A.dp_lanes);
-      KArgs A2 = A;
-      A2.dp_pass = 2;
-      rc = launch_dp_entry<Env>(&A2, model, jit, noise, traj, grid.x, block.x, s);
-    }, s);
-    return rc != MTGP_OK ? rc : lr;
+    if (A.dp_budget <= 0) return launch_dp_entry<Env>(A, model, c);
+    // two launches: every wave for dp_budget attempts, then the parked waves (KArgs.dp_*)
+    if (hipMemsetAsync(A.dp_pending, 0, sizeof(int32_t), c.s) != hipSuccess) return MTGP_ERR_LAUNCH;
+    KArgs A1 = A;
+    A1.dp_pass = 1;
+    int rc = launch_dp_entry<Env>(A1, model, c);
+    if (rc != MTGP_OK) return rc;
+    rc = launch_checked([&] {
+      hipLaunchKernelGGL(k_dp_order, dim3(1), dim3(1024), 0, c.s, A.dp_pending, (const float*)A.dp_state, A.dp_lanes);
+    });
+    if (rc != MTGP_OK) return rc;
+    KArgs A2 = A;
+    A2.dp_pass = 2;
+    return launch_dp_entry<Env>(A2, model, c);
   }
   if (model->model == MTGP_MODEL_STATIC) {
     if constexpr (std::is_same<Env, EnvAcrobot>::value)  // (a unit of its own: MTGP_TU 10)
-      return mtgp_tu_launch_acrobot_static(&A, jit, noise, traj, grid.x, block.x, s);
+      return mtgp_tu_launch_acrobot_static(&A, c);
     else
-      return cs_is_erk(A.m.solver) ? launch_timed([&] { MTGP_CTL_VARIANTS(k_ctl_static, Env, true); }, s)
-                                   : launch_timed([&] { MTGP_CTL_VARIANTS(k_ctl_static, Env, false); }, s);
+      return launch_static<Env>(A, c);
   }
   switch (model->state_size) {
-    case 1: return launch_dyn<Env, 1>(A, jit, noise, traj, grid, block, s);
-    case 2: return launch_dyn<Env, 2>(A, jit, noise, traj, grid, block, s);
-    case 3: return launch_dyn<Env, 3>(A, jit, noise, traj, grid, block, s);
+    case 1: return launch_dyn<Env, 1>(A, c);
+    case 2: return launch_dyn<Env, 2>(A, c);
+    case 3: return launch_dyn<Env, 3>(A, c);
     default:
       if (model->state_size < 4 || model->state_size > kNaWide) return MTGP_ERR_ARG;
-      return model->state_size > kNaRuntime ? launch_dyn<Env, kNaWide>(A, jit, noise, traj, grid, block, s)
-                                            : launch_dyn<Env, kNaRuntime>(A, jit, noise, traj, grid, block, s);
+      return model->state_size > kNaRuntime ? launch_dyn<Env, kNaWide>(A, c) : launch_dyn<Env, kNaRuntime>(A, c);
   }
 }
 
 
 // entries of the split-off environment TUs (hidden: not part of the C ABI)
-#define MTGP_TU_ENTRY_ARGS                                                                              \
-  const void* A, const MtgpModel* model, const MtgpRollouts* ro, bool jit, bool noise, bool traj,       \
-      unsigned grid, unsigned block, hipStream_t s
-__attribute__((visibility("hidden"))) int mtgp_tu_launch_harmonic(MTGP_TU_ENTRY_ARGS);
-__attribute__((visibility("hidden"))) int mtgp_tu_launch_reactor(MTGP_TU_ENTRY_ARGS);
-__attribute__((visibility("hidden"))) int mtgp_tu_launch_acrobot_mask(MTGP_TU_ENTRY_ARGS);
-__attribute__((visibility("hidden"))) int mtgp_tu_launch_acrobot(MTGP_TU_ENTRY_ARGS);
+MTGP_HIDDEN int mtgp_tu_launch_harmonic(const void* A, const MtgpModel* model, const MtgpRollouts* ro, const MtgpLaunchCtx& c);
+MTGP_HIDDEN int mtgp_tu_launch_reactor(const void* A, const MtgpModel* model, const MtgpRollouts* ro, const MtgpLaunchCtx& c);
+MTGP_HIDDEN int mtgp_tu_launch_acrobot_mask(const void* A, const MtgpModel* model, const MtgpRollouts* ro, const MtgpLaunchCtx& c);
+MTGP_HIDDEN int mtgp_tu_launch_acrobot(const void* A, const MtgpModel* model, const MtgpRollouts* ro, const MtgpLaunchCtx& c);
 #if MTGP_DEBUG_CHECKS && defined(MTGP_TU)
 #define MTGP_DBG_CAT2(a, b) a##b
 #define MTGP_DBG_CAT(a, b) MTGP_DBG_CAT2(a, b)
@@ -5554,152 +5501,164 @@ extern "C" int mtgp_ab_fb_count(unsigned long long* host) {  // diagnostic build
 }
 #endif
 #if MTGP_TU_ACRO
-int mtgp_tu_launch_acrobot(MTGP_TU_ENTRY_ARGS) {  // fixed-step solvers (Dopri5 goes on to TU 3)
-  return launch_ctl<EnvAcrobot>(*(const KArgs*)A, model, ro, jit, noise, traj, dim3(grid), dim3(block), s);
+int mtgp_tu_launch_acrobot(const void* A, const MtgpModel* model, const MtgpRollouts* ro, const MtgpLaunchCtx& c) {
+  return launch_ctl<EnvAcrobot>(*(const KArgs*)A, model, ro, c);  // fixed-step solvers (Dopri5 goes on to TU 3)
 }
 #endif
 #if MTGP_TU_ACRO_STATIC
-int mtgp_tu_launch_acrobot_static(const void* Ap, bool jit, bool noise, bool traj, unsigned grid_, unsigned block_,
-                                  hipStream_t s) {
-  const KArgs& A = *(const KArgs*)Ap;
-  const dim3 grid(grid_), block(block_);
-  if (cs_is_erk(A.m.solver)) return launch_timed([&] { MTGP_CTL_VARIANTS(k_ctl_static, EnvAcrobot, true); }, s);
-  return launch_timed([&] { MTGP_CTL_VARIANTS(k_ctl_static, EnvAcrobot, false); }, s);
+int mtgp_tu_launch_acrobot_static(const void* A, const MtgpLaunchCtx& c) {
+  return launch_static<EnvAcrobot>(*(const KArgs*)A, c);
 }
 #endif
 #if MTGP_TU_ACRO_MASK
-int mtgp_tu_launch_acrobot_mask(MTGP_TU_ENTRY_ARGS) {  // every solver; the trajectory variants (traj unused)
-  (void)traj;
-  return launch_ctl<EnvAcrobotMask>(*(const KArgs*)A, model, ro, jit, noise, true, dim3(grid), dim3(block), s);
+int mtgp_tu_launch_acrobot_mask(const void* A, const MtgpModel* model, const MtgpRollouts* ro, const MtgpLaunchCtx& c) {
+  MtgpLaunchCtx t = c;  // every solver; the trajectory variants, whatever the outputs ask for
+  t.traj = true;
+  return launch_ctl<EnvAcrobotMask>(*(const KArgs*)A, model, ro, t);
 }
 #endif
 #if MTGP_TU_ACRO_DOPRI5
-int mtgp_tu_launch_acrobot_dopri5(MTGP_TU_DP_ARGS) {
-  return launch_ctl_dp<EnvAcrobot>(*(const KArgs*)A, model, jit, noise, traj, dim3(grid), dim3(block), s);
+int mtgp_tu_launch_acrobot_dopri5(const void* A, const MtgpModel* model, const MtgpLaunchCtx& c) {
+  return launch_ctl_dp<EnvAcrobot>(*(const KArgs*)A, model, c);
 }
 #endif
 #if MTGP_TU_DP_RT
-int mtgp_tu_launch_dp_rt(const void* Ap, int env, bool wide, bool noise, bool traj, unsigned grid, unsigned block,
-                         hipStream_t s) {
+int mtgp_tu_launch_dp_rt(const void* Ap, int env, bool wide, const MtgpLaunchCtx& c) {
   const KArgs& A = *(const KArgs*)Ap;
-  const dim3 g(grid), b(block);
   switch (env) {
-    case 0: return wide ? launch_dp_rt<EnvAcrobot, kNaWide>(A, noise, traj, g, b, s)
-                        : launch_dp_rt<EnvAcrobot, kNaRuntime>(A, noise, traj, g, b, s);
-    case 1: return wide ? launch_dp_rt<EnvHarmonic, kNaWide>(A, noise, traj, g, b, s)
-                        : launch_dp_rt<EnvHarmonic, kNaRuntime>(A, noise, traj, g, b, s);
-    default: return wide ? launch_dp_rt<EnvReactor, kNaWide>(A, noise, traj, g, b, s)
-                         : launch_dp_rt<EnvReactor, kNaRuntime>(A, noise, traj, g, b, s);
+    case 0: return wide ? launch_dp_rt<EnvAcrobot, kNaWide>(A, c) : launch_dp_rt<EnvAcrobot, kNaRuntime>(A, c);
+    case 1: return wide ? launch_dp_rt<EnvHarmonic, kNaWide>(A, c) : launch_dp_rt<EnvHarmonic, kNaRuntime>(A, c);
+    default: return wide ? launch_dp_rt<EnvReactor, kNaWide>(A, c) : launch_dp_rt<EnvReactor, kNaRuntime>(A, c);
   }
 }
 #endif
 #if MTGP_TU_HARMONIC_DOPRI5
-int mtgp_tu_launch_harmonic_dopri5(MTGP_TU_DP_ARGS) {
-  return launch_ctl_dp<EnvHarmonic>(*(const KArgs*)A, model, jit, noise, traj, dim3(grid), dim3(block), s);
+int mtgp_tu_launch_harmonic_dopri5(const void* A, const MtgpModel* model, const MtgpLaunchCtx& c) {
+  return launch_ctl_dp<EnvHarmonic>(*(const KArgs*)A, model, c);
 }
 #endif
 #if MTGP_TU_REACTOR_DOPRI5
-int mtgp_tu_launch_reactor_dopri5(MTGP_TU_DP_ARGS) {
-  return launch_ctl_dp<EnvReactor>(*(const KArgs*)A, model, jit, noise, traj, dim3(grid), dim3(block), s);
+int mtgp_tu_launch_reactor_dopri5(const void* A, const MtgpModel* model, const MtgpLaunchCtx& c) {
+  return launch_ctl_dp<EnvReactor>(*(const KArgs*)A, model, c);
 }
 #endif
 #if MTGP_TU_HARMONIC
-int mtgp_tu_launch_harmonic(MTGP_TU_ENTRY_ARGS) {
-  return launch_ctl<EnvHarmonic>(*(const KArgs*)A, model, ro, jit, noise, traj, dim3(grid), dim3(block), s);
+int mtgp_tu_launch_harmonic(const void* A, const MtgpModel* model, const MtgpRollouts* ro, const MtgpLaunchCtx& c) {
+  return launch_ctl<EnvHarmonic>(*(const KArgs*)A, model, ro, c);
 }
 #endif
 #if MTGP_TU_REACTOR
-int mtgp_tu_launch_reactor(MTGP_TU_ENTRY_ARGS) {
-  return launch_ctl<EnvReactor>(*(const KArgs*)A, model, ro, jit, noise, traj, dim3(grid), dim3(block), s);
+int mtgp_tu_launch_reactor(const void* A, const MtgpModel* model, const MtgpRollouts* ro, const MtgpLaunchCtx& c) {
+  return launch_ctl<EnvReactor>(*(const KArgs*)A, model, ro, c);
 }
 #endif
 
 
 // the SR kernels (MTGP_TU 8): register-resident n_var <= 4 and the wide-state workgroup kernels
-#define MTGP_TU_SR_ARGS \
-  const void* A_, const MtgpModel* model, bool jit, bool traj, bool dopri5, unsigned G, unsigned Wset, unsigned grid_, \
-      unsigned block_, hipStream_t s
-__attribute__((visibility("hidden"))) int mtgp_tu_launch_sr(MTGP_TU_SR_ARGS);
+MTGP_HIDDEN int mtgp_tu_launch_sr(const void* A, const MtgpModel* model, const MtgpLaunchCtx& c);
 #if MTGP_TU_SR
-int mtgp_tu_launch_sr(MTGP_TU_SR_ARGS) {
+int mtgp_tu_launch_sr(const void* A_, const MtgpModel* model, const MtgpLaunchCtx& c) {
   const KArgs& A = *(const KArgs*)A_;
-  const dim3 grid(grid_), block(block_);
+  const bool dopri5 = model->solver == MTGP_SOLVER_DOPRI5;
+  const bool erk = cs_is_erk(model->solver);  // the two-stage family and Bosh3: kernels of their own
   if (model->n_var > 4) {
     const int nw = (model->n_var + kWideComp - 1) / kWideComp;
-    const dim3 wgrid((unsigned)(((long)A.P + G - 1) / G * Wset)), wblock(kWave * nw);
+    const dim3 wgrid(c.waves), wblock(kWave * nw);
     if (dopri5) {  // + a reduction vector (error norm, MSE)
       const size_t lds_dp = (size_t)(3 * model->n_var + nw * kSMax + nw) * kWave * sizeof(float);
-      return launch_timed([&] {
-        if (jit) {
-          if (traj) hipLaunchKernelGGL((k_sr_wide_dopri5<true, true>), wgrid, wblock, lds_dp, s, A);
-          else hipLaunchKernelGGL((k_sr_wide_dopri5<false, true>), wgrid, wblock, lds_dp, s, A);
-        } else if (traj) hipLaunchKernelGGL((k_sr_wide_dopri5<true, false>), wgrid, wblock, lds_dp, s, A);
-        else hipLaunchKernelGGL((k_sr_wide_dopri5<false, false>), wgrid, wblock, lds_dp, s, A);
-      }, s);
+      return launch_checked([&] {
+        mtgp::sr_variant(c.traj, c.jit, [&](auto T, auto J) {
+          hipLaunchKernelGGL((k_sr_wide_dopri5<T(), J()>), wgrid, wblock, lds_dp, c.s, A);
+        });
+      });
     }
     size_t lds = (size_t)(2 * model->n_var + nw * kSMax + nw) * kWave * sizeof(float);
     if (const char* e = getenv("MTGP_WIDE_LDS_MIN")) {  // diagnostic: fewer workgroups per CU (code working set)
       const long v = atol(e);
       if (v > 0 && (size_t)v > lds && v <= 160 * 1024) lds = (size_t)v;
     }
-    if (cs_is_erk(model->solver))  // the two-stage family and Bosh3: kernels of their own
-      return launch_timed([&] {
-        if (jit) {
-          if (traj) hipLaunchKernelGGL((k_sr_wide<true, true, true>), wgrid, wblock, lds, s, A);
-          else hipLaunchKernelGGL((k_sr_wide<false, true, true>), wgrid, wblock, lds, s, A);
-        } else if (traj) hipLaunchKernelGGL((k_sr_wide<true, false, true>), wgrid, wblock, lds, s, A);
-        else hipLaunchKernelGGL((k_sr_wide<false, false, true>), wgrid, wblock, lds, s, A);
-      }, s);
-    return launch_timed([&] {
-      if (jit) {
-        if (traj) hipLaunchKernelGGL((k_sr_wide<true, true>), wgrid, wblock, lds, s, A);
-        else hipLaunchKernelGGL((k_sr_wide<false, true>), wgrid, wblock, lds, s, A);
-      } else if (traj) hipLaunchKernelGGL((k_sr_wide<true, false>), wgrid, wblock, lds, s, A);
-      else hipLaunchKernelGGL((k_sr_wide<false, false>), wgrid, wblock, lds, s, A);
-    }, s);
+    return launch_checked([&] {
+      mtgp::with_flag(erk, [&](auto ERK) {
+        constexpr bool kErk = ERK();
+        mtgp::sr_variant(c.traj, c.jit, [&](auto T, auto J) {
+          hipLaunchKernelGGL((k_sr_wide<T(), J(), kErk>), wgrid, wblock, lds, c.s, A);
+        });
+      });
+    });
   }
-#define MTGP_SR(NV)                                                                                       \
-  case NV:                                                                                                \
-  return launch_timed([&] {                                                                             \
-    if (dopri5) {                                                                                       \
-      if (jit) {                                                                                        \
-        if (traj) hipLaunchKernelGGL((k_sr_dopri5<NV, true, true>), grid, block, 0, s, A);              \
-        else hipLaunchKernelGGL((k_sr_dopri5<NV, false, true>), grid, block, 0, s, A);                  \
-      } else if (traj) hipLaunchKernelGGL((k_sr_dopri5<NV, true, false>), grid, block, 0, s, A);        \
-      else hipLaunchKernelGGL((k_sr_dopri5<NV, false, false>), grid, block, 0, s, A);                   \
-    } else if (erk) {                                                                                   \
-      if (jit) {                                                                                        \
-        if (traj) hipLaunchKernelGGL((k_sr<NV, true, true, true>), grid, block, 0, s, A);               \
-        else hipLaunchKernelGGL((k_sr<NV, false, true, true>), grid, block, 0, s, A);                   \
-      } else if (traj) hipLaunchKernelGGL((k_sr<NV, true, false, true>), grid, block, 0, s, A);         \
-      else hipLaunchKernelGGL((k_sr<NV, false, false, true>), grid, block, 0, s, A);                    \
-    } else if (jit) {                                                                                   \
-      if (traj) hipLaunchKernelGGL((k_sr<NV, true, true>), grid, block, 0, s, A);                       \
-      else hipLaunchKernelGGL((k_sr<NV, false, true>), grid, block, 0, s, A);                           \
-    } else if (traj) hipLaunchKernelGGL((k_sr<NV, true, false>), grid, block, 0, s, A);                 \
-    else hipLaunchKernelGGL((k_sr<NV, false, false>), grid, block, 0, s, A);                            \
-  }, s);
-  const bool erk = cs_is_erk(model->solver);  // the two-stage family and Bosh3: kernels of their own
-  switch (model->n_var) {
-    MTGP_SR(1)
-    MTGP_SR(2)
-    MTGP_SR(3)
-    MTGP_SR(4)
-    default: return MTGP_ERR_ARG;
-  }
-#undef MTGP_SR
-  return MTGP_ERR_ARG;
+  if (model->n_var < 1) return MTGP_ERR_ARG;
+  return launch_checked([&] {
+    mtgp::int_variant<1, 2, 3, 4>(model->n_var, [&](auto NVc) {
+      constexpr int NV = NVc();
+      if (dopri5) {
+        mtgp::sr_variant(c.traj, c.jit, [&](auto T, auto J) {
+          hipLaunchKernelGGL((k_sr_dopri5<NV, T(), J()>), c.grid, c.block, 0, c.s, A);
+        });
+      } else {
+        mtgp::with_flag(erk, [&](auto ERK) {
+          constexpr bool kErk = ERK();
+          mtgp::sr_variant(c.traj, c.jit, [&](auto T, auto J) {
+            hipLaunchKernelGGL((k_sr<NV, T(), J(), kErk>), c.grid, c.block, 0, c.s, A);
+          });
+        });
+      }
+    });
+  });
 }
 #endif
 
 #if MTGP_TU_MAIN
-// a split-off TU's launch, timed with this TU's events (mtgp_last_kernel_ms)
-template <class F>
-int launch_tu(F&& entry, hipStream_t s) {
-  int rc = MTGP_OK;
-  const int lr = launch_timed([&] { rc = entry(); }, s);
-  return rc != MTGP_OK ? rc : lr;
+namespace {
+
+// Kernel timing (mtgp_set_timing / mtgp_last_kernel_ms / mtgp_kernel_ms_history), owned by this
+// unit alone: one interval per evaluator call, around the unit entry that launches its kernels.  The
+// switch is process-wide; the event pairs (a ring of the last kTimingRing calls, so a caller can
+// read the durations of a whole run after one synchronisation instead of stalling the queue every
+// launch) are per host thread and re-created when the thread moves to another device, so concurrent
+// callers on different threads / streams / devices never share events.
+std::atomic<bool> g_timing{false};
+constexpr int kTimingRing = 1024;
+struct TimingState {
+  hipEvent_t ev0[kTimingRing] = {}, ev1[kTimingRing] = {};
+  int device = -1;
+  long long count = 0;  // timed launches recorded on `device`
+  void reset(int dev) {
+    for (int i = 0; i < kTimingRing; ++i)
+      if (ev0[i]) { (void)hipEventDestroy(ev0[i]); (void)hipEventDestroy(ev1[i]); ev0[i] = ev1[i] = nullptr; }
+    device = dev;
+    count = 0;
+  }
+};
+thread_local TimingState t_timing;
+
+float timing_ms(const TimingState& ts, long long i) {
+  const int k = (int)(i % kTimingRing);
+  float ms = -1.0f;
+  (void)hipEventElapsedTime(&ms, ts.ev0[k], ts.ev1[k]);
+  return ms;
 }
+
+// a unit entry's launches (`entry` returns its ABI code), timed as one interval on stream s
+template <class F>
+int launch_timed(F&& entry, hipStream_t s) {
+  const bool timing = g_timing.load(std::memory_order_relaxed);
+  TimingState& ts = t_timing;
+  int k = 0;
+  if (timing) {
+    int dev = -1;
+    (void)hipGetDevice(&dev);
+    if (ts.device != dev) ts.reset(dev);
+    k = (int)(ts.count % kTimingRing);
+    if (!ts.ev0[k]) { (void)hipEventCreate(&ts.ev0[k]); (void)hipEventCreate(&ts.ev1[k]); }
+    (void)hipEventRecord(ts.ev0[k], s);
+  }
+  const int rc = entry();
+  if (hipGetLastError() != hipSuccess) return rc != MTGP_OK ? rc : MTGP_ERR_LAUNCH;
+  if (timing) { (void)hipEventRecord(ts.ev1[k], s); ++ts.count; }
+  return rc;
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -6138,7 +6097,7 @@ int mtgp_eval_rk4_jit(const MtgpModel* model, const MtgpInstr* prog, const int32
   if ((int64_t)P * n_prog * L * (int64_t)sizeof(MtgpInstr) > UINT32_MAX) return MTGP_ERR_ARG;  // 32-bit program offsets
   const bool dopri5 = model->solver == MTGP_SOLVER_DOPRI5;
   // fixed step: RK4, Euler and (ABI v24) Heun, Midpoint, Ralston, Bosh3
-  const bool erk = model->solver >= MTGP_SOLVER_HEUN && model->solver <= MTGP_SOLVER_BOSH3;
+  const bool erk = cs_is_erk(model->solver);
   if (model->solver != MTGP_SOLVER_RK4 && model->solver != MTGP_SOLVER_EULER && !dopri5 && !erk) return MTGP_ERR_ARG;
   if (dopri5) {  // adaptive: save points come from ts, steps from the controller
     if (model->model == MTGP_MODEL_SR && (model->n_var < 1 || model->n_var > MTGP_MAX_DATA)) return MTGP_ERR_ARG;
@@ -6227,27 +6186,28 @@ int mtgp_eval_rk4_jit(const MtgpModel* model, const MtgpInstr* prog, const int32
   if (noise && (!rollouts->obs_w || model->model == MTGP_MODEL_SR)) return MTGP_ERR_ARG;
   if (model->prng_impl != MTGP_PRNG_THREEFRY_ORIGINAL && model->prng_impl != MTGP_PRNG_THREEFRY_PARTITIONABLE)
     return MTGP_ERR_ARG;
-  const int rc = [&]() -> int {
+  const MtgpLaunchCtx c{traj, noise, jit, grid.x, block.x, (unsigned)waves, s};
+  // every kernel lives behind its unit's entry; the one timed interval spans the entry's launches
+  int (*ctl_entry)(const void*, const MtgpModel*, const MtgpRollouts*, const MtgpLaunchCtx&) = nullptr;
   if (model->model == MTGP_MODEL_DYNAMIC || model->model == MTGP_MODEL_STATIC) {
     switch (model->env) {
-      case MTGP_ENV_ACROBOT:
-        if (rollouts->fit_kof)  // the general cost mask: its own kernels (EnvAcrobotMask, TU 6)
-          return launch_tu([&] { return mtgp_tu_launch_acrobot_mask(&A, model, rollouts, jit, noise, traj, grid.x, block.x, s); }, s);
-        return launch_tu([&] { return mtgp_tu_launch_acrobot(&A, model, rollouts, jit, noise, traj, grid.x, block.x, s); }, s);
-      case MTGP_ENV_HARMONIC_OSCILLATOR:
-        return launch_tu([&] { return mtgp_tu_launch_harmonic(&A, model, rollouts, jit, noise, traj, grid.x, block.x, s); }, s);
-      case MTGP_ENV_STIRRED_TANK_REACTOR:
-        return launch_tu([&] { return mtgp_tu_launch_reactor(&A, model, rollouts, jit, noise, traj, grid.x, block.x, s); }, s);
+      case MTGP_ENV_ACROBOT:  // (the general cost mask: its own kernels, EnvAcrobotMask, TU 6)
+        ctl_entry = rollouts->fit_kof ? mtgp_tu_launch_acrobot_mask : mtgp_tu_launch_acrobot;
+        break;
+      case MTGP_ENV_HARMONIC_OSCILLATOR: ctl_entry = mtgp_tu_launch_harmonic; break;
+      case MTGP_ENV_STIRRED_TANK_REACTOR: ctl_entry = mtgp_tu_launch_reactor; break;
       default: return MTGP_ERR_ARG;
     }
   } else if (model->model == MTGP_MODEL_SR) {
     if (!rollouts->ys_true) return MTGP_ERR_ARG;
     if (model->n_var > 4 && (model->n_var > MTGP_MAX_DATA || n_prog < model->prog_state + model->n_var))
       return MTGP_ERR_ARG;
-    return launch_tu([&] { return mtgp_tu_launch_sr(&A, model, jit, traj, dopri5, (unsigned)G, (unsigned)Wset, grid.x, block.x, s); }, s);
+  } else {
+    return MTGP_ERR_ARG;
   }
-  return MTGP_ERR_ARG;
-  }();
+  const int rc = launch_timed([&] {
+    return ctl_entry ? ctl_entry(&A, model, rollouts, c) : mtgp_tu_launch_sr(&A, model, c);
+  }, s);
   if (rc != MTGP_OK || Wset == 1) return rc;
   hipLaunchKernelGGL(k_rollout_mean, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, s, out->rollout_fitness, P,
                      rollouts->R, model->max_fitness, model->parsimony, nodes, out->fitness);

@@ -20,22 +20,28 @@ def code_object(path, tmp):
 
 def kernels(path):
     with tempfile.TemporaryDirectory() as tmp:
-        co = code_object(path, tmp)
-        notes = subprocess.run([f"{LLVM}/llvm-readelf", "--notes", co], check=True, capture_output=True,
-                               text=True).stdout
-    out, cur = [], {}
+        return kernels_of(code_object(path, tmp))
+
+
+def kernels_of(co):
+    """The metadata entries of an unbundled code object."""
+    notes = subprocess.run([f"{LLVM}/llvm-readelf", "--notes", co], check=True, capture_output=True,
+                           text=True).stdout
+    out, cur = [], None
     for line in notes.splitlines():
-        m = re.match(r"\s+\.(name|vgpr_count|sgpr_count|vgpr_spill_count|sgpr_spill_count|"
-                     r"private_segment_fixed_size|agpr_count):\s+(\S+)", line)
-        if not m:
-            continue
-        k, v = m.groups()
-        if k == "name":
-            cur = {"name": v}
+        # an entry of amdhsa.kernels starts at "  - .key:"; its own keys (sorted: .agpr_count comes
+        # before .name) sit at that depth, the keys of its .args deeper
+        m = re.match(r"  (- |  )\.(name|vgpr_count|sgpr_count|vgpr_spill_count|sgpr_spill_count|"
+                     r"private_segment_fixed_size|group_segment_fixed_size|kernarg_segment_size|agpr_count):"
+                     r"\s+(\S+)", line)
+        if line.startswith("  - "):
+            cur = {}
             out.append(cur)
-        else:
-            cur[k] = int(v)
-    return out
+        if not m or cur is None:
+            continue
+        k, v = m.group(2), m.group(3)
+        cur[k] = v if k == "name" else int(v)
+    return [k for k in out if "name" in k]
 
 
 if __name__ == "__main__":

@@ -243,6 +243,33 @@ def test_jit_matches_interpreter(kind):
         assert bits_equal(a[k], b[k]), mismatch_report(a[k], b[k], k)
 
 
+@pytest.mark.parametrize("kind,noise,jit", [("dynamic", False, False), ("dynamic", True, False),
+                                            ("static", False, False), ("static", True, False), ("static", True, True),
+                                            ("sr", False, False), ("sr_wide", False, False)])
+def test_fitness_only_variants_bitexact(kind, noise, jit):
+    """The fitness-only (TRAJ = false) kernel variants that no other case of the parity, solver,
+    cost-mask and API files launches -- interpreter with and without observation noise, the static
+    policy's JIT code under noise, k_sr and k_sr_wide (n_var 5) interpreted -- against the oracle:
+    3 individuals, 2 rollouts, 8 steps of h = 0.05, 3 save points."""
+    P, R = 3, 2
+    if kind in ("dynamic", "static"):
+        setup = dynamic_setup if kind == "dynamic" else static_setup
+        env, lib, ff, data, pop = setup(P=P, R=R, n_steps=8, obs_noise=0.1 if noise else 0.0, seed=41)
+        data = mt.control_data(ff.env, R, 0.2, None, seed=42, n_steps=2)  # save points 4 steps apart
+    else:
+        env, lib, ff, data, pop = sr_setup(P=P, R=R, n_save=3, save_every=4, h=0.05, seed=41,
+                                           n_var=2 if kind == "sr" else 5)
+    eng = DeviceEngine(ff, lib, 0.0, "cuda:0", jit=jit)
+    res = eng.evaluate(torch.from_numpy(np.ascontiguousarray(pop)).cuda(), data, trajectories=False,
+                       rollout_fitness=True)
+    torch.cuda.synchronize()
+    assert DeviceEngine.jit_ok(res["_flat"]) == jit
+    d = eng.prepare_data(data)
+    assert (d["n_steps"], d["n_save"]) == (8, 3)
+    ref = orc.evaluate(oracle_model(ff, d), pop, lib, oracle_rollouts(d), trajectories=False)
+    _check(res, ref, P, R, [])
+
+
 def test_jit_slow_sin_cos_lanes_fall_back_to_interpreter():
     """Coefficients scaled by 1e6: sin/cos arguments beyond 2^17 take the spec's slow
     reduction, which the JIT code reports and the evaluator re-runs with the interpreter."""
