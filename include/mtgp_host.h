@@ -10,6 +10,18 @@
  * Draws come from per-(population, pair) xoshiro256** streams derived from `seed`: results are
  * reproducible for a seed and independent of the thread count, and distributed like the
  * reference's (which splits JAX keys per operation), not draw-for-draw equal to it.
+ *
+ * The library is csrc/mtgp_evolve_core.h -- the code the device kernels of libmtgp_hip.so run
+ * (include/mtgp.h, mtgp_evolve_device) -- behind a thread pool, so both take the same arguments:
+ *   1 <= N <= 256, 1 <= num_pop, num_trees <= 65535, num_pop * pop_size <= 2^27,
+ *   2 <= n_funcs <= 128 with slots[] in 0..2, op_index[] in [0, n_funcs),
+ *   0 <= var_start <= n_funcs - n_vars, 1 <= max_init_depth <= 30, 1 <= tournament_size <= 64,
+ *   0 <= elite_size <= pop_size, every reproduction_prob > 0 (the per-tree mask is redrawn until
+ *   it selects a tree), no null table.
+ * Anything else is rejected with -1.  Arrays need float alignment only.  A population that breaks
+ * the tree layout gives an unspecified result, never an access outside the arrays.  Fitness may
+ * hold any bits: in the elitism and migration orders NaN comes after every number, ascending and
+ * descending alike, and ties keep index order.
  */
 #ifndef MTGP_HOST_H
 #define MTGP_HOST_H

@@ -1,6 +1,7 @@
 // mtgp_evolve.hip -- the evolution step on the device (ABI v22): the population stays on the GPU
-// between generations.  The algorithm is csrc/mtgp_evolve_core.h (the host library's operators in
-// the same draw order); this file is the launch geometry and the C entry points.
+// between generations.  The algorithm is csrc/mtgp_evolve_core.h (the one implementation, which
+// the host library runs too); this file is the launch geometry and the C entry points.  The host
+// twins at the end run the core's CPU drivers serially (mtgp_evo::Serial): test instruments.
 //
 // A generation is three launches on the caller's stream, no host synchronisation, no D2H copy:
 //   k_evo_order   one thread per candidate: its stable ascending and descending fitness ranks (counted)
@@ -143,11 +144,14 @@ extern "C" int mtgp_sample_population_device(int32_t num_pop, int32_t pop_size, 
 extern "C" int mtgp_evolve_device_host(const float* populations, const float* fitness, int32_t num_pop,
                                        int32_t pop_size, int32_t num_trees, int32_t N, const MtgpEvolveConfig* cfg,
                                        uint64_t seed, float* out) {
+  // the device entry's 16-B rule (the kernels move rows as float4), kept so both reject alike
+  if ((((uintptr_t)populations) | ((uintptr_t)out)) & 15u) return MTGP_ERR_ARG;
   const int rc = host_evolve(populations, fitness, num_pop, pop_size, num_trees, N, cfg, seed, out);
   return rc < 0 ? MTGP_ERR_ARG : rc;
 }
 
 extern "C" int mtgp_sample_population_device_host(int32_t num_pop, int32_t pop_size, int32_t num_trees, int32_t N,
                                                   const MtgpEvolveConfig* cfg, uint64_t seed, float* out) {
+  if ((uintptr_t)out & 15u) return MTGP_ERR_ARG;
   return host_sample(num_pop, pop_size, num_trees, N, cfg, seed, out) < 0 ? MTGP_ERR_ARG : MTGP_OK;
 }

@@ -1,8 +1,19 @@
-// mtgp_evolve_core.h -- the evolution step of csrc/mtgp_evolve.cpp restated allocation-free, with
-// bounded buffers, for the host and the device (MTGP_HD): the same operators in the same draw
-// order, so a generation computed here equals the host library's draw for draw.  The host library
-// stays as it is (its golden digests pin it); this header is the second implementation the parity
-// tests hold against it (tests/test_device_evolve_host.py, tests/test_gpu_device_evolve.py).
+// mtgp_evolve_core.h -- the evolution step (the reference's genetic_operators/, gp.py:475-525):
+// the one C++ implementation, allocation-free with bounded buffers, compiled for the host and the
+// device (MTGP_HD).  The host library (csrc/mtgp_evolve.cpp, libmtgp_host.so) and the k_evo_*
+// kernels (csrc/mtgp_evolve.hip) are drivers around it, so a generation is the same draw for draw
+// wherever it runs.  Same operators, probabilities and array contract as the numpy restatement
+// (multitreegp_amd/genetic_operators.py, the tested spec): a tree is float32 [N, 4] rows
+// [f, a, b, value], empty rows packed low, root at row N-1, descending rows in preorder,
+// a = k-1, b = k-1-|subtree(a)|.  Edits are done on the preorder node list and written back.
+// tests/test_host_evolve.py and tests/golden/evolve_parity.json pin the output bit for bit.
+//
+// Random numbers: xoshiro256** streams, one per (population, pair) or sampled candidate, derived
+// from the seed.  Runs are distributed like the reference's (JAX threefry keys split per
+// operation), not draw for draw.
+//
+// References: initialization.py:9-164 (sample_tree), mutation.py:9-579, crossover.py:8-218,
+// reproduction.py:8-176, genetic_programming.py:475-525.
 //
 // Execution model.  A "group" of lanes (one wave on the device, one lane on the host) handles one
 // (population, pair) or one sampled candidate.  Every lane runs the pair's xoshiro256** stream and
@@ -24,8 +35,12 @@
 #include <math.h>
 #include <stddef.h>
 #include <stdint.h>
-#include <stdlib.h>
 #include <string.h>
+
+#include <algorithm>
+#include <new>
+#include <numeric>
+#include <vector>
 
 #include "mtgp_f32math.h"
 #include "mtgp_host.h"
@@ -253,8 +268,8 @@ MTGP_HD inline void copy_rows(float* dst, const float* src, int rows, Lanes L) {
 
 // ---------------------------------------------------------------- fitness ordering
 // Total order for any bits: NaN last, +-0 tie, the index breaks ties.  For NaN-free input the
-// ranks are std::stable_sort's with the comparators of mtgp_evolve.cpp (F[a] < F[b], and
-// -F[a] < -F[b] for the descending order).
+// ranks are those of a stable sort by F[a] < F[b] (and by -F[a] < -F[b] for the descending order),
+// the reference's argsort.  The kernel counts ranks (order_ranks); the host driver sorts.
 MTGP_HD inline bool fit_less(float a, float b) { return a < b || (a == a && b != b); }
 MTGP_HD inline bool fit_greater(float a, float b) { return a > b || (a == a && b != b); }
 MTGP_HD inline bool fit_same(float a, float b) { return a == b || (a != a && b != b); }
@@ -341,8 +356,10 @@ MTGP_HD inline int choose_var(const Cfg& C, Rng& g, int tr) {
   return g.choice(C.var_mask + (size_t)tr * C.n_vars, C.n_vars);
 }
 
-// initialization.py:9-124 for one tree (see mtgp_evolve.cpp Ops::sample_tree); the preorder list
-// goes to out[0, cap), the node count is returned (counted past cap, never written past it)
+// initialization.py:9-124 for one tree: breadth-first draws, operators only while
+// open_slots < N - i - 1 and depth + 1 < depth_limit, leaf = coefficient w.p. 0.5 else an allowed
+// variable.  The preorder list (descending depth-first rows) goes to out[0, cap), the node count
+// is returned (counted past cap, never written past it)
 MTGP_HD inline int sample_tree(const Ctx& X, Rng& g, int depth_limit, int tr, Node* out, int cap) {
   const Cfg& C = X.C;
   const int N = C.N, tree_size = (int)((1u << C.depth) - 1u), I = tree_size < 2 * N - 1 ? tree_size : 2 * N - 1;
@@ -399,8 +416,8 @@ MTGP_HD inline Node new_leaf(const Ctx& X, Rng& g, int tr) {  // mutation.py:60,
 MTGP_HD inline int new_operator(const Ctx& X, Rng& g) { return X.C.op_index[g.choice(X.C.op_prob, X.C.n_ops)]; }
 
 // The empty-row count (f == 0) and the lowest row of the preorder (one above the highest row whose
-// f truncates to 0), as mtgp_evolve.cpp's scan and mutate_tree count them -- the one pass over all
-// N rows, done by the lanes together.  In a valid tree rows [0, lo) are exactly the empty rows, so
+// f truncates to 0, where to_preorder stops) -- the one pass over all N rows, done by the lanes
+// together.  In a valid tree rows [0, lo) are exactly the empty rows, so
 // the serial loops below start at lo: empty rows weigh nothing in any choice.
 struct RowInfo {
   int e, lo;
@@ -615,9 +632,12 @@ MTGP_HD inline void mutate_tree(const Ctx& X, const float* t, Rng& g, int tr, fl
 }
 
 // ------------------------------------------------------------------ crossover
-// the crossover's pass over a tree's rows (mtgp_evolve.cpp Ops::scan): weight prefix sums c and
-// subtree sizes sz.  Rows [0, ri.lo) -- the empty rows of a valid tree: weight 0, size 1 -- are
-// filled by the lanes together; the recurrence runs over the tree's own rows only.
+// The crossover's pass over a tree's rows, low to high: the row weights (crossover.py: 0 empty,
+// 2 operator, 1 leaf) as prefix sums c -- small integers, so Rng::choice's running subtraction and
+// choose_prefix's binary search pick the same row for every draw -- and every row's subtree size sz
+// from the arities (the operands of row k are the subtrees rooted at k-1 and just below it).  Rows
+// [0, ri.lo) -- the empty rows of a valid tree: weight 0, size 1 -- are filled by the lanes
+// together; the recurrence runs over the tree's own rows only.
 MTGP_HD inline void scan(const Cfg& C, const float* t, RowInfo ri, int32_t* c, int32_t* sz, Lanes L) {
   const int N = C.N, nf = C.n_funcs;
   for (int k = L.lane; k < ri.lo; k += L.n) c[k + 1] = 0, sz[k] = 1;
@@ -672,8 +692,13 @@ MTGP_HD inline bool cx_invalid_e(const float* t1, const float* t2, int N, int i1
   return e1 < s2 - s1 || e2 < s1 - s2 || equal;
 }
 
-// mtgp_evolve.cpp Ops::splice_rows with the output rows split over the lanes: every row's source
-// and operand size follow from the two scans alone
+// One crossover offspring written straight from the parents' rows (the same result as splicing the
+// preorder lists through rebuild, without them): `a`'s rows above ia, then `b`'s subtree at ib (sb
+// rows), then `a`'s rows below its subtree at ia (sa rows), each row
+// [f, k-1 | -1, k-1-|subtree(k-1)| | -1, value if coefficient] as from_preorder writes it.  The
+// subtree sizes of `a`'s rows above ia are a's own plus (sb - sa) for the ancestors of ia.  `a`
+// and `b` may be the same tree (both tournaments picked one candidate).  The output rows are split
+// over the lanes: every row's source and operand size follow from the two scans alone
 MTGP_HD inline void splice_rows(const Ctx& X, const float* a, const int32_t* za, int lo_a, int ia, int sa,
                                 const float* b, const int32_t* zb, int ib, int sb, float* o) {
   const Cfg& C = X.C;
@@ -866,8 +891,9 @@ MTGP_HD inline void sample_candidate(const Ctx& X, long b, float* out) {
 }
 
 // ------------------------------------------------------------------ host side
-// Argument checks, the configuration blob and the CPU drivers (the "host twins" of the kernels:
-// the same core code, looping where the device uses a grid).
+// Argument checks, the configuration blob and the CPU drivers (the same core code, looping where
+// the device uses a grid): the host library runs them on its threads, the "host twins" in
+// libmtgp_hip.so serially.
 // the configuration alone (what the blob is packed from)
 inline bool config_ok(int32_t num_pop, int32_t T, const MtgpEvolveConfig* c) {
   if (!c || num_pop < 1 || num_pop > 65535 || T < 1 || T > 65535) return false;
@@ -935,59 +961,79 @@ inline Cfg make_cfg(const MtgpEvolveConfig* c, int num_pop, int pop_size, int T,
   return C;
 }
 
-// mtgp_evolve_populations on the core code; returns the output population size, -1 on bad arguments
-inline int host_evolve(const float* pops, const float* fitness, int32_t num_pop, int32_t pop_size, int32_t T,
-                       int32_t N, const MtgpEvolveConfig* c, uint64_t seed, float* out) {
-  if (!pops || !fitness || !out || !args_ok(num_pop, pop_size, T, N, c)) return -1;
-  if ((((uintptr_t)pops) | ((uintptr_t)out)) & 15u) return -1;
-  char* blob = (char*)malloc(blob_bytes(c, num_pop, T));
-  char* wsmem = (char*)malloc(ws_bytes(N) + 16);
-  int32_t* ord = (int32_t*)malloc(sizeof(int32_t) * 2 * (size_t)num_pop * pop_size);
-  int rc = -1;
-  if (blob && wsmem && ord) {
-    pack_blob(c, num_pop, T, blob);
-    const Cfg C = make_cfg(c, num_pop, pop_size, T, N, seed, blob);
-    const Ctx X{C, ws_carve((void*)(((uintptr_t)wsmem + 15) & ~(uintptr_t)15), N), Lanes{0, 1}, C.pow07};
-    int32_t* asc = ord;
-    int32_t* desc = ord + (size_t)num_pop * pop_size;
-    for (int i = 0; i < num_pop; ++i)
-      for (int j = 0; j < pop_size; ++j) {
-        int ra, rd;
-        order_ranks(fitness + (size_t)i * pop_size, pop_size, j, &ra, &rd);
-        asc[(size_t)i * pop_size + ra] = j;
-        desc[(size_t)i * pop_size + rd] = j;
-      }
-    Gen G;
-    G.pops = pops, G.fitness = fitness, G.asc = asc, G.desc = desc, G.out = out;
-    const int E = c->elite_size, n_pairs = (pop_size - E) / 2;
-    for (int i = 0; i < num_pop; ++i) {
-      for (int e = 0; e < E; ++e) elite_rows(X.C, G, i, e, X.L);
-      for (int k = 0; k < n_pairs; ++k) reproduce_pair(X, G, i, k);
-    }
-    rc = E + 2 * n_pairs;
+// The CPU drivers.  `run(n, grain, body)` is the caller's executor: it calls body(lo, hi) on
+// disjoint ranges that cover [0, n), on at most n / grain threads.  Every range carves a workspace
+// of its own and every pair / candidate owns its random stream and its output rows, so the result
+// does not depend on how the ranges are cut.  Serial is the executor of a caller without threads.
+struct Serial {
+  template <class F>
+  void operator()(long n, long, F body) const {
+    body(0L, n);
   }
-  free(ord);
-  free(wsmem);
-  free(blob);
-  return rc;
+};
+
+struct HostWs {  // one worker's workspace
+  std::vector<char> mem;
+  Ws W;
+  explicit HostWs(int N)
+      : mem(ws_bytes(N) + 16), W(ws_carve((void*)(((uintptr_t)mem.data() + 15) & ~(uintptr_t)15), N)) {}
+};
+
+// mtgp_evolve_populations; returns the output population size, -1 on bad arguments or no memory
+template <class Exec = Serial>
+inline int host_evolve(const float* pops, const float* fitness, int32_t num_pop, int32_t pop_size, int32_t T,
+                       int32_t N, const MtgpEvolveConfig* c, uint64_t seed, float* out, Exec run = Exec()) try {
+  if (!pops || !fitness || !out || !args_ok(num_pop, pop_size, T, N, c)) return -1;
+  std::vector<char> blob(blob_bytes(c, num_pop, T));
+  pack_blob(c, num_pop, T, blob.data());
+  const Cfg C = make_cfg(c, num_pop, pop_size, T, N, seed, blob.data());
+  // the orders k_evo_order counts (order_ranks), sorted: fit_less / fit_greater are strict weak
+  // orders for any bits and the stable sort breaks their ties by index, as the ranks do
+  std::vector<int32_t> ord(2 * (size_t)num_pop * pop_size);
+  int32_t* asc = ord.data();
+  int32_t* desc = asc + (size_t)num_pop * pop_size;
+  for (int i = 0; i < num_pop; ++i) {
+    const float* F = fitness + (size_t)i * pop_size;
+    int32_t* a = asc + (size_t)i * pop_size;
+    int32_t* d = desc + (size_t)i * pop_size;
+    std::iota(a, a + pop_size, 0);
+    std::iota(d, d + pop_size, 0);
+    std::stable_sort(a, a + pop_size, [F](int32_t x, int32_t y) { return fit_less(F[x], F[y]); });
+    std::stable_sort(d, d + pop_size, [F](int32_t x, int32_t y) { return fit_greater(F[x], F[y]); });
+  }
+  Gen G;
+  G.pops = pops, G.fitness = fitness, G.asc = asc, G.desc = desc, G.out = out;
+  const int E = c->elite_size, n_pairs = (pop_size - E) / 2;
+  const long grain = 65536L / ((long)T * N);  // a thread per >= 64K tree rows of offspring
+  for (int i = 0; i < num_pop; ++i) {
+    for (int e = 0; e < E; ++e) elite_rows(C, G, i, e, Lanes{0, 1});
+    run((long)n_pairs, grain < 1 ? 1L : grain, [&C, &G, i, N](long lo, long hi) {
+      const HostWs ws(N);
+      const Ctx X{C, ws.W, Lanes{0, 1}, C.pow07};
+      for (long k = lo; k < hi; ++k) reproduce_pair(X, G, i, (int)k);
+    });
+  }
+  return E + 2 * n_pairs;
+} catch (const std::bad_alloc&) {
+  return -1;
 }
 
+// mtgp_sample_population; returns 0, -1 on bad arguments or no memory
+template <class Exec = Serial>
 inline int host_sample(int32_t num_pop, int32_t pop_size, int32_t T, int32_t N, const MtgpEvolveConfig* c,
-                       uint64_t seed, float* out) {
-  if (!out || !args_ok(num_pop, pop_size, T, N, c) || ((uintptr_t)out & 15u)) return -1;
-  char* blob = (char*)malloc(blob_bytes(c, num_pop, T));
-  char* wsmem = (char*)malloc(ws_bytes(N) + 16);
-  int rc = -1;
-  if (blob && wsmem) {
-    pack_blob(c, num_pop, T, blob);
-    const Cfg C = make_cfg(c, num_pop, pop_size, T, N, seed, blob);
-    const Ctx X{C, ws_carve((void*)(((uintptr_t)wsmem + 15) & ~(uintptr_t)15), N), Lanes{0, 1}, C.pow07};
-    for (long b = 0; b < (long)num_pop * pop_size; ++b) sample_candidate(X, b, out);
-    rc = 0;
-  }
-  free(wsmem);
-  free(blob);
-  return rc;
+                       uint64_t seed, float* out, Exec run = Exec()) try {
+  if (!out || !args_ok(num_pop, pop_size, T, N, c)) return -1;
+  std::vector<char> blob(blob_bytes(c, num_pop, T));
+  pack_blob(c, num_pop, T, blob.data());
+  const Cfg C = make_cfg(c, num_pop, pop_size, T, N, seed, blob.data());
+  run((long)num_pop * pop_size, 256L, [&C, N, out](long lo, long hi) {
+    const HostWs ws(N);
+    const Ctx X{C, ws.W, Lanes{0, 1}, C.pow07};
+    for (long b = lo; b < hi; ++b) sample_candidate(X, b, out);
+  });
+  return 0;
+} catch (const std::bad_alloc&) {
+  return -1;
 }
 
 }  // namespace mtgp_evo

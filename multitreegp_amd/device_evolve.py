@@ -1,13 +1,14 @@
 """Device-side evolution step (include/mtgp.h ABI v22, csrc/mtgp_evolve.hip): the population stays
 on the GPU between generations.  DeviceEvolver mirrors host.HostEvolver -- the same strategy
-parameters packed into the same MtgpEvolveConfig -- and computes what the host library computes,
-draw for draw (csrc/mtgp_evolve_core.h): columns f, a, b bit for bit, values to within 1 float32
+parameters packed into the same MtgpEvolveConfig -- and runs the code the host library runs
+(csrc/mtgp_evolve_core.h), draw for draw: columns f, a, b bit for bit, values to within 1 float32
 ulp where the device's f64 log rounds differently inside a normal draw.
 
 evolve / sample_population enqueue on the current stream and return fresh CUDA tensors from
 torch's stream-ordered allocator: an output never aliases an input or memory the caller can still
-see.  evolve_host / sample_population_host run the same core code on the CPU (the host twins the
-parity tests compare with HostEvolver bit for bit)."""
+see.  evolve_host / sample_population_host run the same core code on the CPU, serially, inside
+libmtgp_hip.so (the host twins: tests/test_device_evolve_host.py holds them and HostEvolver to the
+same recorded digests)."""
 from __future__ import annotations
 
 import ctypes

@@ -1,7 +1,8 @@
 """ctypes binding of the native host library (include/mtgp_host.h, csrc/mtgp_evolve.cpp): the
-evolution step of GeneticProgramming (gp.py:475-525) in C++ with OpenMP, so the host work of a
-generation is milliseconds next to the GPU evaluation.  multitreegp_amd.genetic_operators is the
-numpy restatement it is tested against (distributions and layout invariants)."""
+evolution step of GeneticProgramming (gp.py:475-525) in C++ on std::threads -- the code of
+csrc/mtgp_evolve_core.h, which the device kernels run too -- so the host work of a generation is
+milliseconds next to the GPU evaluation.  multitreegp_amd.genetic_operators is the numpy
+restatement it is tested against (distributions and layout invariants)."""
 from __future__ import annotations
 
 import ctypes

@@ -170,6 +170,16 @@ def test_hip_sources_cover_every_included_header():
             assert os.path.realpath(h) in listed, f"{h} (included by {src}) is missing from HIP_SOURCES"
 
 
+def test_host_sources_cover_every_included_header():
+    """HOST_SOURCES decides when libmtgp_host.so is rebuilt: the same closure for its one source."""
+    import __graft_entry__ as ge
+    listed = {os.path.realpath(p) for p in ge.HOST_SOURCES}
+    srcs = [p for p in ge.HOST_SOURCES if p.endswith(".cpp")]
+    assert srcs == [ge.HOST_SOURCES[0]]  # build_host compiles HOST_SOURCES[0]
+    for h in _local_includes(srcs[0], set()):
+        assert os.path.realpath(h) in listed, f"{h} (included by {srcs[0]}) is missing from HOST_SOURCES"
+
+
 def test_build_info_matches_tree():
     """Build provenance by content: the library embeds the SHA-256 of the sources it was built from."""
     import __graft_entry__ as ge

@@ -1,9 +1,13 @@
-"""Device evolve, CPU side: the host twins (mtgp_evolve_device_host / mtgp_sample_population_device_host)
-run the kernels' core code (csrc/mtgp_evolve_core.h) on the CPU and must equal the host library
-(HostEvolver, csrc/mtgp_evolve.cpp) bit for bit over whole arrays -- same seed, same draws, glibc's
-log on both sides, so no allowance.  Plus memory safety on malformed populations (guard regions and
-a sanitized stand-alone program), argument errors without a GPU, and the strategy's backend switch."""
+"""The evolution step's one C++ implementation (csrc/mtgp_evolve_core.h) on the CPU, through both
+of its drivers: the host library (HostEvolver, csrc/mtgp_evolve.cpp, threads) and the host twins of
+libmtgp_hip.so (mtgp_evolve_device_host / mtgp_sample_population_device_host, serial).  Both must
+reproduce, bit for bit over whole arrays, the digests recorded from the separate host library this
+header replaced (tests/golden/evolve_parity.json) -- same seed, same draws, glibc's log, so no
+allowance.  Plus memory safety on malformed populations (guard regions and sanitized stand-alone
+programs), the argument domain without a GPU, and the strategy's backend switch."""
 import ctypes
+import hashlib
+import json
 import os
 import subprocess
 
@@ -38,31 +42,101 @@ def same_bits(a, b):
     return a.shape == b.shape and np.array_equal(a.view(np.uint32), b.view(np.uint32))
 
 
-@pytest.mark.parametrize("rtp", [(1.0, 0.0, 0.0), (0.0, 1.0, 0.0), (0.0, 0.0, 1.0), (0.9, 0.1, 0.0)],
-                         ids=["crossover", "mutation", "resample", "mixed"])
+# ---------------------------------------------------------------------- parity
+# Each case yields, in order, every array its comparison covers.  `host` samples the parents;
+# `side` is what is under test: the HostEvolver itself or the Twin of the DeviceEvolver.
+GOLDEN = os.path.join(ROOT, "tests", "golden", "evolve_parity.json")
+
+
+class Twin:
+    def __init__(self, dev):
+        self.evolve, self.sample_population = dev.evolve_host, dev.sample_population_host
+
+
+def _one_generation(host, side):
+    parents = host.sample_population(2048, seed=3)
+    fit = np.random.default_rng(4).random((1, 2048)).astype(np.float32)
+    yield side.evolve(parents, fit, seed=11, current_generation=0)
+
+
+def _twenty_chained(host, side):
+    pops = host.sample_population(128, seed=3)
+    rng = np.random.default_rng(0)
+    for gen in range(20):
+        fit = rng.random((2, 128)).astype(np.float32)
+        pops = side.evolve(pops, fit, seed=100 + gen, current_generation=gen).copy()
+        yield pops
+
+
+def _tied_migration(host, side):
+    pops = host.sample_population(64, seed=7)
+    fit = (np.random.default_rng(8).integers(0, 4, (3, 64)) * 0.25).astype(np.float32)
+    yield side.evolve(pops, fit, seed=1, current_generation=0)
+
+
+def _two_generations(host, side):
+    pops = host.sample_population(128, seed=5)
+    fit = np.random.default_rng(6).random((1, 128)).astype(np.float32)
+    for gen in range(2):
+        pops = side.evolve(pops, fit, seed=21 + gen, current_generation=gen).copy()
+        yield pops
+
+
+def _sampled(S):
+    def run(host, side):
+        yield side.sample_population(S, seed=1)
+    return run
+
+
+RTPS = {"crossover": (1.0, 0.0, 0.0), "mutation": (0.0, 1.0, 0.0), "resample": (0.0, 0.0, 1.0),
+        "mixed": (0.9, 0.1, 0.0)}
+CHUNKS = {"N64": (64, 10, 3), "N128": (128, 16, 2), "N7": (7, 3, 3)}
+SAMPLES = {"3000-40-5": (3000, 40, 5), "64-128-16": (64, 128, 16)}
+# case id -> (trees, evolvers() keywords, the arrays it yields)
+PARITY_CASES = {
+    **{f"one_generation[{k}]": (3, dict(E=40, rtp=rtp), _one_generation) for k, rtp in RTPS.items()},
+    "twenty_chained": (3, dict(N=20, depth=4, E=4, rtp=(0.5, 0.4, 0.1), num_pop=2, migration_size=4, period=3),
+                       _twenty_chained),
+    **{f"tied_migration[{E}]": (3, dict(E=E, num_pop=3, migration_size=6, period=1), _tied_migration)
+       for E in (64, 0)},
+    **{f"row_chunk_edges[{k}]": (T, dict(N=N, depth=depth, E=8, rtp=(0.5, 0.4, 0.1)), _two_generations)
+       for k, (N, depth, T) in CHUNKS.items()},
+    **{f"sample_population[{k}]": (3, dict(N=N, depth=depth), _sampled(S)) for k, (S, N, depth) in SAMPLES.items()},
+}
+
+
+def parity_digests(case):
+    """{"host": [...], "twin": [...]}: the sha256 of every array of the case, from each side."""
+    T, kw, run = PARITY_CASES[case]
+    host, dev = evolvers(_lib(T), **kw)
+    sha = lambda a: hashlib.sha256(np.ascontiguousarray(a, np.float32).tobytes()).hexdigest()  # noqa: E731
+    return {"host": [sha(a) for a in run(host, host)], "twin": [sha(a) for a in run(host, Twin(dev))]}
+
+
+def assert_recorded(case):
+    """The host library and the twin are one implementation now, so each is held against what the
+    two-implementation parent produced: digests of whole arrays recorded from its libmtgp_host.so
+    (scripts/record_evolve_parity.py; its twin hashed to the same values)."""
+    with open(GOLDEN) as f:
+        want = json.load(f)["cases"][case]
+    got = parity_digests(case)
+    for side in ("host", "twin"):
+        assert len(got[side]) == len(want)
+        for k, (g, w) in enumerate(zip(got[side], want)):
+            assert g == w, f"{side}, array {k}"
+
+
+@pytest.mark.parametrize("rtp", list(RTPS))
 def test_one_generation_equals_host_library(rtp):
     """S 2048, E 40, T 3, N 40, depth 5: about 1,000 pairs per operator mix (the all-mutation case
     runs every one of the seven mutations and both arities of the operator-changing ones)."""
-    host, dev = evolvers(_lib(), E=40, rtp=rtp)
-    parents = host.sample_population(2048, seed=3)
-    fit = np.random.default_rng(4).random((1, 2048)).astype(np.float32)
-    ref = host.evolve(parents, fit, seed=11, current_generation=0)
-    got = dev.evolve_host(parents, fit, seed=11, current_generation=0)
-    assert same_bits(got, ref)
+    assert_recorded(f"one_generation[{rtp}]")
 
 
 def test_twenty_chained_generations_equal():
     """N 20, depth 4 (size limits and retry loops hit constantly), 2 populations, migration size 4
     every 3rd generation, fresh random fitness: equal at every generation."""
-    host, dev = evolvers(_lib(), N=20, depth=4, E=4, rtp=(0.5, 0.4, 0.1), num_pop=2, migration_size=4, period=3)
-    pops = host.sample_population(128, seed=3)
-    rng = np.random.default_rng(0)
-    for gen in range(20):
-        fit = rng.random((2, 128)).astype(np.float32)
-        ref = host.evolve(pops, fit, seed=100 + gen, current_generation=gen)
-        got = dev.evolve_host(pops, fit, seed=100 + gen, current_generation=gen)
-        assert same_bits(got, ref), f"generation {gen}"
-        pops = ref.copy()
+    assert_recorded("twenty_chained")
 
 
 @pytest.mark.parametrize("E", [64, 0])
@@ -70,32 +144,19 @@ def test_migration_with_tied_fitness(E):
     """3 populations of 64, migration 6 every generation, fitness quantised to 4 values: the
     stable descending order (receiver) is not the reverse of the stable ascending one (sender,
     elitism), and selection uses the pre-migration fitness."""
-    host, dev = evolvers(_lib(), E=E, num_pop=3, migration_size=6, period=1)
-    pops = host.sample_population(64, seed=7)
-    fit = (np.random.default_rng(8).integers(0, 4, (3, 64)) * 0.25).astype(np.float32)
-    ref = host.evolve(pops, fit, seed=1, current_generation=0)
-    got = dev.evolve_host(pops, fit, seed=1, current_generation=0)
-    assert same_bits(got, ref)
+    assert_recorded(f"tied_migration[{E}]")
 
 
-@pytest.mark.parametrize("N,depth,T", [(64, 10, 3), (128, 16, 2), (7, 3, 3)], ids=["N64", "N128", "N7"])
+@pytest.mark.parametrize("N,depth,T", list(CHUNKS.values()), ids=list(CHUNKS))
 def test_row_chunk_edges(N, depth, T):
     """One 64-row chunk exactly; two chunks with I = 2N - 1 in sample_tree; smaller than a chunk
-    (empty < 8 always).  S 128, mixed operators."""
-    host, dev = evolvers(_lib(T), N=N, depth=depth, E=8, rtp=(0.5, 0.4, 0.1))
-    pops = host.sample_population(128, seed=5)
-    fit = np.random.default_rng(6).random((1, 128)).astype(np.float32)
-    for gen in range(2):
-        ref = host.evolve(pops, fit, seed=21 + gen, current_generation=gen)
-        got = dev.evolve_host(pops, fit, seed=21 + gen, current_generation=gen)
-        assert same_bits(got, ref), f"generation {gen}"
-        pops = ref.copy()
+    (empty < 8 always).  S 128, mixed operators, two generations."""
+    assert_recorded(next(f"row_chunk_edges[{k}]" for k, v in CHUNKS.items() if v == (N, depth, T)))
 
 
-@pytest.mark.parametrize("S,N,depth", [(3000, 40, 5), (64, 128, 16)])
+@pytest.mark.parametrize("S,N,depth", list(SAMPLES.values()))
 def test_sample_population_equals_host_library(S, N, depth):
-    host, dev = evolvers(_lib(), N=N, depth=depth)
-    assert same_bits(dev.sample_population_host(S, seed=1), host.sample_population(S, seed=1))
+    assert_recorded(f"sample_population[{S}-{N}-{depth}]")
 
 
 # ------------------------------------------------------------------ malformed input
@@ -148,23 +209,28 @@ def test_malformed_population_stays_inside_its_buffers(kind):
     assert np.array_equal(pv, before)  # inputs are read only
 
 
-_ASAN_MAIN = r"""
+_SAN_MAIN = r"""
 #include <stdio.h>
+#include <string.h>
 #include <vector>
-#include "mtgp_evolve_core.h"
+#include "mtgp_host.h"
 static uint64_t state = 0x1234567ull;
 static uint32_t rnd() { state = state * 6364136223846793005ull + 1442695040888963407ull; return (uint32_t)(state >> 32); }
-int main() {
-  const int P = 3, S = 32, T = 2, N = 24, n_funcs = 8, n_ops = 3, n_vars = 3;
+// S 32, T 2: too few tree rows for a second thread (the driver's serial path); S 352, T 64: 174
+// pairs of 1536 rows and 1056 sampled candidates, four threads' worth for both entries
+static int run(int S, int T) {
+  const int P = 3, N = 24, n_funcs = 8, n_ops = 3, n_vars = 3;
   int32_t slots[n_funcs] = {0, 0, 2, 2, 1, 0, 0, 0}, op_index[n_ops] = {2, 3, 4};
   double op_prob[n_ops] = {0.5, 0.3, 0.2}, tp[P * 4], rtp[P * 3] = {0.4, 0.5, 0.1, 0.0, 1.0, 0.0, 1.0, 0.0, 0.0},
          rp[P] = {1.0, 0.7, 0.5};
-  float var_mask[T * n_vars] = {1, 1, 1, 0, 1, 1};
+  std::vector<float> var_mask((size_t)T * n_vars, 1.0f);
+  for (int t = 1; t < T; t += 2) var_mask[(size_t)t * n_vars] = 0.0f;
   for (int i = 0; i < P * 4; ++i) tp[i] = 0.25;
-  MtgpEvolveConfig c = {n_funcs, slots, n_ops, op_index, op_prob, 5, n_vars, var_mask, 4, 1.0f, 0, 1, 5, 4, 4, tp, rtp, rp};
+  MtgpEvolveConfig c = {n_funcs, slots, n_ops, op_index, op_prob, 5, n_vars, var_mask.data(), 4, 1.0f, 0, 1, 5, 4, 4,
+                        tp, rtp, rp};
   const size_t n = (size_t)P * S * T * N * 4;
   for (int round = 0; round < 3; ++round) {
-    // heap blocks of the exact size (no slack for the sanitizer to miss), 16-B aligned by new
+    // heap blocks of the exact size (no slack for the sanitizer to miss)
     std::vector<float> pops(n), out(n), fit((size_t)P * S);
     for (size_t i = 0; i < n; ++i) {
       uint32_t b = rnd();
@@ -177,7 +243,7 @@ int main() {
       memcpy(&pops[i], &b, 4);
     }
     if (round == 2) {  // valid parents, hostile fitness only
-      if (mtgp_evo::host_sample(P, S, T, N, &c, 9, pops.data()) != 0) return 2;
+      if (mtgp_sample_population(P, S, T, N, &c, 9, pops.data()) != 0) return 2;
     }
     for (size_t i = 0; i < fit.size(); ++i) {
       uint32_t b = rnd();
@@ -186,33 +252,51 @@ int main() {
     }
     for (int gen = 0; gen < 2; ++gen) {
       c.current_generation = gen;
-      if (mtgp_evo::host_evolve(pops.data(), fit.data(), P, S, T, N, &c, 77 + gen, out.data()) != S) return 3;
+      if (mtgp_evolve_populations(pops.data(), fit.data(), P, S, T, N, &c, 77 + gen, out.data()) != S) return 3;
       if (round == 2) pops = out;
     }
   }
+  return 0;
+}
+int main() {
+  if (int rc = run(32, 2)) return rc;
+  if (int rc = run(352, 64)) return rc;
   puts("evolve core: clean");
   return 0;
 }
 """
 
 
-def test_malformed_population_under_sanitizers(tmp_path):
-    """The core header in a stand-alone program of its own (g++ -fsanitize=address,undefined), run
-    as a child process on malformed populations and fitness."""
+def _sanitized_run(tmp_path, san):
+    """The host library's translation unit (the core header behind its threaded driver) in a
+    stand-alone program of its own, compiled with `san` and run as a child process with 4 threads
+    on malformed populations and fitness."""
     cxx = os.environ.get("CXX", "g++")
-    san = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all"]
     probe = tmp_path / "probe.cpp"
-    probe.write_text("int main() { return 0; }\n")
-    if subprocess.run([cxx, *san, str(probe), "-o", str(tmp_path / "probe")], capture_output=True).returncode != 0 \
+    probe.write_text("#include <thread>\nint main() { std::thread t([] {}); t.join(); return 0; }\n")
+    if subprocess.run([cxx, *san, "-pthread", str(probe), "-o", str(tmp_path / "probe")],
+                      capture_output=True).returncode != 0 \
             or subprocess.run([str(tmp_path / "probe")], capture_output=True).returncode != 0:
-        pytest.skip("no sanitized program can be linked and run here")
-    src = tmp_path / "evo_asan.cpp"
-    src.write_text(_ASAN_MAIN)
-    exe = tmp_path / "evo_asan"
-    subprocess.run([cxx, "-std=c++17", "-O1", "-g", "-ffp-contract=off", *san, "-I", os.path.join(ROOT, "include"),
-                    "-I", os.path.join(ROOT, "multitreegp_amd", "csrc"), str(src), "-o", str(exe)], check=True)
-    r = subprocess.run([str(exe)], capture_output=True, text=True)
+        pytest.skip("no program sanitized this way can be linked and run here")
+    src = tmp_path / "evo_san.cpp"
+    src.write_text(_SAN_MAIN)
+    exe = tmp_path / "evo_san"
+    csrc = os.path.join(ROOT, "multitreegp_amd", "csrc")
+    subprocess.run([cxx, "-std=c++17", "-O1", "-g", "-ffp-contract=off", "-pthread", *san, "-I",
+                    os.path.join(ROOT, "include"), "-I", csrc, str(src), os.path.join(csrc, "mtgp_evolve.cpp"),
+                    "-o", str(exe)], check=True)
+    r = subprocess.run([str(exe)], capture_output=True, text=True, env={**os.environ, "MTGP_HOST_THREADS": "4"})
     assert r.returncode == 0 and "clean" in r.stdout, r.stdout + r.stderr
+
+
+def test_malformed_population_under_sanitizers(tmp_path):
+    """g++ -fsanitize=address,undefined: no access outside the buffers, no undefined arithmetic."""
+    _sanitized_run(tmp_path, ["-fsanitize=address,undefined", "-fno-sanitize-recover=all"])
+
+
+def test_threaded_driver_under_thread_sanitizer(tmp_path):
+    """g++ -fsanitize=thread: the workers share only what they read."""
+    _sanitized_run(tmp_path, ["-fsanitize=thread"])
 
 
 # --------------------------------------------------------------------- arguments
@@ -259,6 +343,53 @@ def test_argument_errors_without_a_gpu():
     assert lib.mtgp_evolve_workspace_bytes(0, 8) == nat.ERR_ARG
     with pytest.raises(ValueError):
         dev.evolve_host(pops[:, :, :2], fit, 0, 0)
+
+
+@pytest.mark.parametrize("what", ["N257", "tournament65", "reproduction_prob0"])
+def test_host_library_rejects_what_the_device_rejects(what):
+    """The host entries take the core's argument domain (include/mtgp_host.h): trees over 256
+    nodes, tournaments over 64 and a reproduction probability of 0 (tree_mask would redraw for
+    ever) are ValueErrors from HostEvolver.evolve and sample_population alike."""
+    N, ts, rp = {"N257": (257, 7, 1.0), "tournament65": (40, 65, 1.0), "reproduction_prob0": (40, 7, 0.0)}[what]
+    ev = HostEvolver(_lib(), N, 5, 1.0, 10, 0, ts, 0, np.ones((1, ts)), np.array([[0.9, 0.1, 0.0]]), np.array([rp]), 1)
+    pops = np.zeros((1, 8, 3, N, 4), np.float32)
+    pops[..., N - 1, 0] = 1.0  # every tree one coefficient: a valid population
+    pops[..., 1:3] = -1.0
+    with pytest.raises(ValueError):
+        ev.evolve(pops, np.zeros((1, 8), np.float32), seed=1, current_generation=0)
+    with pytest.raises(ValueError):
+        ev.sample_population(8, seed=1)
+    ok = HostEvolver(_lib(), 256, 5, 1.0, 10, 0, 64, 0, np.ones((1, 64)), np.array([[0.9, 0.1, 0.0]]),
+                     np.array([1e-3]), 1)  # the bounds themselves are inside the domain
+    assert ok.evolve(ok.sample_population(8, seed=1), np.zeros((1, 8), np.float32), 1, 0).shape == (1, 8, 3, 256, 4)
+
+
+def test_host_library_takes_any_float_aligned_array():
+    """The 16-byte rule is the device entry's and the twins' (test_argument_errors_without_a_gpu);
+    mtgp_evolve_populations and mtgp_sample_population copy rows with memcpy: arrays 4 bytes off a
+    16-byte boundary give the bits of aligned ones."""
+    host, _ = evolvers(_lib(), E=4, rtp=(0.5, 0.4, 0.1), num_pop=2, migration_size=3, period=1)
+    S = 48
+
+    def off4(shape):
+        raw = np.zeros(int(np.prod(shape)) + 8, np.float32)
+        a = raw[(-raw.ctypes.data // 4) % 4 + 1:][:int(np.prod(shape))].reshape(shape)
+        assert a.ctypes.data % 16 == 4
+        return a
+
+    pops = host.sample_population(S, seed=2)
+    fit = np.random.default_rng(1).random((2, S)).astype(np.float32)
+    ref = host.evolve(pops, fit, seed=9, current_generation=0)
+    assert pops.ctypes.data % 16 == 0 and ref.ctypes.data % 16 == 0
+    p4, o4, s4 = off4(pops.shape), off4(ref.shape), off4(pops.shape)
+    p4[:] = pops
+    assert same_bits(host.evolve(p4, fit, seed=9, current_generation=0), ref)  # the input alone
+    f32p = ctypes.POINTER(ctypes.c_float)
+    rc = host.lib.mtgp_evolve_populations(p4.ctypes.data_as(f32p), fit.ctypes.data_as(f32p), 2, S, 3, host.N,
+                                          ctypes.byref(host.cfg), 9, o4.ctypes.data_as(f32p))
+    assert rc == S and same_bits(o4, ref)  # input and output
+    assert host.lib.mtgp_sample_population(2, S, 3, host.N, ctypes.byref(host.cfg), 2, s4.ctypes.data_as(f32p)) == 0
+    assert same_bits(s4, pops)
 
 
 def test_strategy_accepts_the_device_backend():
