@@ -16,8 +16,9 @@
 //     exactly one word.
 // The output (program words, lengths, status) is the one flatten_tree produces, word for word
 // (tests/test_gpu_build.py compares with the host flattener).  A tree in which one row is reached
-// from two parents (a shared sub-DAG, only in arbitrary arrays) needs its subtree emitted twice;
-// such a lane re-runs the serial flatten_tree.
+// from two parents (a shared sub-DAG, only in arbitrary arrays) needs its subtree emitted twice:
+// k_flatten's lane re-runs the serial flatten_tree, k_flatten_wave walks it with one lane
+// (u_serial_walk below).
 #pragma once
 #include "mtgp_flatten.h"
 
@@ -90,6 +91,199 @@ MTGP_INLINE MTGP_HD int u_unary_leaf(int fn, const ULeaf& la, bool push, MtgpIns
   return 2;
 }
 MTGP_INLINE MTGP_HD bool u_leaf(uint32_t w) { return u_isc(w) || u_kind(w) == K_VAR; }
+
+// --------------------------------------------------------------------------------------
+// The wave flattener's per-row core (k_flatten_wave: one lane per row).  `Tab` is one program's
+// tables, indexed by row: w (u_pack record), len (unfused length low 16, saturated | fused length
+// high 16), cv (folded constant), val (the original value column), pos (pass 2 link, below),
+// flag.  The kernel keeps them in LDS; tests/test_flatten_core_host.py runs the same functions
+// over plain arrays, row after row, against flatten_tree.
+
+// operand row jj of row i: an evaluated row (its table entry) or, for jj >= i, the original value
+// column (gp.py:366-369)
+struct UOperand {
+  uint32_t w;
+  ULeaf lf;
+  int len, flen;
+  bool leaf;
+};
+
+template <class Tab>
+MTGP_INLINE MTGP_HD UOperand u_operand(const Tab& S, int jj, int i) {
+  UOperand o;
+  if (jj < i) {
+    o.w = S.w[jj];
+    const uint32_t ln = S.len[jj];
+    o.len = (int)(ln & 0xffffu);
+    o.flen = (int)(ln >> 16);
+    o.lf.isc = u_isc(o.w);
+    o.lf.v = S.cv[jj];
+    o.lf.slot = u_slot(o.w);
+    o.leaf = u_leaf(o.w);
+  } else {
+    o.w = u_pack(K_CONST, 0, 0, 1, 1, 0);
+    o.lf.isc = true;
+    o.lf.v = S.val[jj];
+    o.lf.slot = 0;
+    o.len = o.flen = 1;
+    o.leaf = true;
+  }
+  return o;
+}
+
+// pass 1: operator row i (function fn, operand rows ja, jb) once its operand rows < i are resolved
+template <class Tab>
+MTGP_INLINE MTGP_HD void u_resolve_op(Tab& S, int i, int fn, int ja, int jb) {
+  const int ar = fn_arity(fn);
+  uint32_t kind = ar == 1 ? K_UNARY : K_BINARY, isc = 1, afirst = 1, need = 0;
+  int len = 1, flen = 1;
+  float cv = 0.0f;
+  const UOperand a = u_operand(S, ja, i);
+  UOperand b;
+  b.w = 0; b.lf.isc = true; b.lf.v = 0.0f; b.lf.slot = 0; b.len = b.flen = 1; b.leaf = true;
+  if (ar == 2) b = u_operand(S, jb, i);
+  if (a.lf.isc && b.lf.isc) {  // constant subtree: folded with the kernel's fp32 primitives
+    cv = apply_fn(fn, a.lf.v, ar == 1 ? 0.0f : b.lf.v);
+  } else {
+    isc = 0;
+    if (ar == 1) {
+      if (a.leaf) { len = 2; flen = unary_fuses(fn) ? 1 : 2; }
+      else { len = a.len + 1; flen = a.flen + 1; need = u_need(a.w); }
+    } else if (a.leaf && b.leaf) {
+      len = 2; flen = 1;
+    } else if (b.leaf) {
+      len = a.len + 1; flen = a.flen + 1; need = u_need(a.w);
+    } else if (a.leaf) {
+      len = b.len + 1; flen = b.flen + 1; need = u_need(b.w);
+    } else {
+      const uint32_t pa = u_need(a.w), qb = u_need(b.w);
+      len = a.len + b.len + 1;
+      flen = a.flen + b.flen + 1;
+      if (pa >= qb) { afirst = 1; need = pa > qb + 1 ? pa : qb + 1; }
+      else { afirst = 0; need = qb > pa + 1 ? qb : pa + 1; }
+    }
+  }
+  S.w[i] = u_pack(kind, (uint32_t)fn, 0, isc, afirst, need > 31u ? 31u : need);
+  S.len[i] = (uint32_t)(len > 65535 ? 65535 : len) | (uint32_t)(flen > 65535 ? 65535 : flen) << 16;
+  S.cv[i] = cv;
+}
+
+// Pass 2 in closed form.  The code of a non-leaf node is [first operand subtree][second operand
+// subtree][own word], so a node's first word is the sum, over its path to the root, of what lies
+// in front of it inside its parent: 0 for the operand evaluated first, the first operand's fused
+// length for the second.  A node pushes the accumulator iff some link of that path is a second
+// operand (the first operand inherits its parent's push).  Every non-leaf row writes one link per
+// non-leaf operand row (u_claim: parent row | offset << 8 | second << 24 in pos[operand], and
+// bump(operand) counts the claims); after that each row adds up its own path (u_walk), with no
+// synchronisation between the levels.  A row claimed twice needs its code twice: u_serial_walk.
+constexpr uint32_t kULinkNone = 0xffffffffu;
+MTGP_INLINE MTGP_HD uint32_t u_link(int row, int off, bool second) {
+  return (uint32_t)row | (uint32_t)off << 8 | (second ? 1u << 24 : 0u);
+}
+static_assert(MTGP_MAX_NODES <= 256, "u_link holds a row in 8 bits");
+
+template <class Tab, class Bump>
+MTGP_INLINE MTGP_HD void u_claim(Tab& S, int i, int ca, int cb, Bump bump) {
+  const uint32_t w = S.w[i];  // (the caller passes non-leaf rows only: an operator, not folded)
+  auto claim = [&](int c, int off, bool second) {
+    S.pos[c] = u_link(i, off, second);
+    bump(c);
+  };
+  const UOperand a = u_operand(S, ca, i);
+  if (u_kind(w) == K_UNARY) {
+    if (!a.leaf) claim(ca, 0, false);
+    return;
+  }
+  const UOperand b = u_operand(S, cb, i);
+  if (a.leaf && b.leaf) return;
+  if (b.leaf) claim(ca, 0, false);
+  else if (a.leaf) claim(cb, 0, false);
+  else {
+    const bool af = u_afirst(w) != 0;
+    claim(af ? ca : cb, 0, false);
+    claim(af ? cb : ca, af ? a.flen : b.flen, true);
+  }
+}
+
+// first word of row i's code | push << 16, or -1 if the root does not reach row i.  A link points
+// to a higher row, so the path ends.
+template <class Tab>
+MTGP_INLINE MTGP_HD int u_walk(const Tab& S, int i, int root) {
+  int pos = 0;
+  uint32_t push = 0;
+  for (int cur = i; cur != root;) {
+    const uint32_t e = S.pos[cur];
+    if (e == kULinkNone) return -1;
+    pos += (int)((e >> 8) & 0xffffu);
+    push |= e >> 24;
+    cur = (int)(e & 255u);
+  }
+  return pos | (int)(push << 16);
+}
+
+// the word(s) of non-leaf row i (operand rows ca, cb) whose code starts at pos: emit(at, word);
+// visit(row, pos, push) names its non-leaf operand rows and where their code starts
+template <class Tab, class Emit, class Visit>
+MTGP_INLINE MTGP_HD void u_emit_node(const Tab& S, int i, int ca, int cb, int pos, bool push, Emit emit,
+                                     Visit visit) {
+  const uint32_t w = S.w[i];
+  const int fn = (int)u_fn(w);
+  const UOperand a = u_operand(S, ca, i);
+  if (u_kind(w) == K_UNARY) {
+    if (a.leaf) {
+      MtgpInstr w2[2];
+      const int nw = u_unary_leaf(fn, a.lf, push, w2);
+      emit(pos, w2[0]);  // (nw is 1 or 2; no dynamic index into w2, which would put it in scratch)
+      if (nw > 1) emit(pos + 1, w2[1]);
+    } else {
+      visit(ca, pos, push);
+      emit(pos + a.flen, u_instr(unary_op(fn), 0, 0.0f));
+    }
+    return;
+  }
+  const UOperand b = u_operand(S, cb, i);
+  if (a.leaf && b.leaf) {
+    MtgpInstr x;
+    fuse_pair(u_load(a.lf, push), u_op_leaf(fn, 0, b.lf), &x);
+    emit(pos, x);
+  } else if (b.leaf) {
+    visit(ca, pos, push);
+    emit(pos + a.flen, u_op_leaf(fn, 0, b.lf));
+  } else if (a.leaf) {
+    visit(cb, pos, push);
+    emit(pos + b.flen, u_op_leaf(fn, 1, a.lf));
+  } else {
+    const bool af = u_afirst(w) != 0;
+    const int f1 = af ? a.flen : b.flen, f2 = af ? b.flen : a.flen;
+    visit(af ? ca : cb, pos, push);
+    visit(af ? cb : ca, pos + f1, true);
+    emit(pos + f1 + f2, u_op_stack(fn, af ? 1 : 0));
+  }
+}
+
+// The same words for a tree in which a row has two parents (arbitrary arrays only): one caller
+// walks from the root with a stack of (row, pos, push) frames kept in pos[0 .. stack_cap), so a
+// shared row is emitted once per path, as flatten_tree's emit_program does.  The lengths of pass 1
+// already count it once per path, so the positions are the closed form above.  The stack holds at
+// most one waiting operand per level and a level's row index is below its parent's: <= N frames.
+// kids(row, ca, cb) gives a row's operand rows.  Returns false after more than `cap` nodes (cannot
+// happen while the root's unfused length is <= cap; the bound keeps a broken table from looping).
+template <class Tab, class Emit, class Kids>
+MTGP_INLINE MTGP_HD bool u_serial_walk(Tab& S, int root, int cap, int stack_cap, Emit emit, Kids kids) {
+  int top = 0, seen = 0;
+  S.pos[0] = u_link(root, 0, false);
+  while (top >= 0) {
+    const uint32_t e = S.pos[top--];
+    if (++seen > cap) return false;
+    const int i = (int)(e & 255u);
+    int ca = 0, cb = 0;
+    kids(i, ca, cb);
+    u_emit_node(S, i, ca, cb, (int)((e >> 8) & 0xffffu), (e >> 24) != 0u, emit, [&](int c, int cpos, bool cpush) {
+      if (top + 1 < stack_cap) S.pos[++top] = u_link(c, cpos, cpush);
+    });
+  }
+  return true;
+}
 
 // per-lane bit set over NMAX rows kept in registers (selects, never a dynamic index)
 template <int NMAX>

@@ -3580,7 +3580,7 @@ __global__ void __launch_bounds__(256) k_eval_programs(const MtgpInstr* __restri
 // flight while the current ones are resolved.  Optionally the lane also sizes its program's JIT
 // translation (jit_words: fall-through code words, < 0 if untranslatable; jit_cost: the schedule
 // weight), so the JIT build needs no translation pass of its own before the code is emitted.
-constexpr int32_t kFlatSerial = 0x7fff;  // status of a program left to k_flatten_serial
+constexpr int32_t kFlatSerial = 0x7fff;  // status of a program k_flatten (lane) leaves to k_flatten_serial
 
 // JIT sizing of one flattened program (mtgp_flatten_ex jit_words / jit_cost)
 __device__ __forceinline__ void flat_jit_size(const MtgpInstr* out, int L, int n, int32_t* jit_words_out,
@@ -3639,15 +3639,18 @@ JitOpTable jit_op_table() {
 }
 
 // LP: the lanes sizing one program (the wave, or a 32-lane half of it -- k_flatten_wave's two
-// programs per wave); lane = the lane within them, KI chunks of LP instructions
-template <int KI, int LP = kWave>
+// programs per wave); lane = the lane within them.  Chunks of LP instructions, as many as the
+// longer of the wave's programs needs (every lane of the wave takes part in every chunk's
+// shuffles and ballots; was a fixed five chunks for the longest program a tree can give).
+template <int LP = kWave>
 __device__ __forceinline__ void flat_jit_size_wave(const MtgpInstr* prog, int n, const JitOpTable& T,
                                                    int32_t* jit_words_out, int32_t* jit_cost_out, size_t pj, int lane) {
   const int shift = LP == kWave ? 0 : (int)(threadIdx.x & (kWave - 1) & ~(LP - 1));  // this segment's first lane
   int words = 0, sub = 0, carry = 0, rc = 0;
   bool failed = false;
-#pragma unroll
-  for (int k = 0; k < KI; ++k) {
+  int n_wave = uni(n);  // (the upper half's lanes are gone when the last wave has one program)
+  if (LP < kWave && (__ballot(true) >> LP) != 0ull) n_wave = max(n_wave, __builtin_amdgcn_readlane(n, LP));
+  for (int k = 0; k * LP < n_wave; ++k) {
     const int i = k * LP + lane;
     const bool in = i < n;
     int d = 0, e = 0;
@@ -3703,30 +3706,32 @@ __device__ __forceinline__ void flat_jit_size_wave(const MtgpInstr* prog, int n,
 // then a slot is preloaded iff fewer than kJitPreSlots slots occur before it.  Status as in
 // jit_program: a slot >= MTGP_MAX_DATA anywhere (its preload scan runs first), else the first
 // opcode / stack error in program order.  fpos: MTGP_MAX_DATA ints of this wave's LDS.
-template <int KI>
 __device__ __forceinline__ void flat_jit_size_wave_lds(const MtgpInstr* prog, int n, const JitOpTable& T,
                                                        int32_t* jit_words_out, int32_t* jit_cost_out, size_t pj,
                                                        int lane, int* fpos) {
   static_assert(MTGP_MAX_DATA <= kWave, "one lane per data slot");
   if (lane < MTGP_MAX_DATA) fpos[lane] = 0x7fffffff;
   __syncthreads();
-  int sa[KI], sb[KI];  // this lane's data-operand slots per chunk (-1: none)
+  // instruction x's data-operand slots (-1: none)
+  auto slots = [&](const MtgpInstr& x, uint32_t f, int& sa, int& sb) {
+    uint32_t ib;
+    __builtin_memcpy(&ib, &x.imm, 4);
+    sa = (f & kOpIbSlot) ? (int)(ib / MTGP_SLOT_BYTES) : -1;
+    sb = (f & kOpAxSlot) ? (int)((x.op & 0xffffffu) / MTGP_SLOT_BYTES) : -1;
+  };
   bool far = false;
-#pragma unroll
-  for (int k = 0; k < KI; ++k) {
+  const int n_wave = uni(n);  // chunks of 64 instructions, as many as the program has
+  for (int k = 0; k * kWave < n_wave; ++k) {
     const int i = k * kWave + lane;
-    sa[k] = sb[k] = -1;
     if (i < n) {
       const MtgpInstr x = prog[i];
       const uint32_t code = x.op >> MTGP_OP_SHIFT;
       const uint32_t f = code < 64u ? T.flags[code] : 0u;
-      uint32_t ib;
-      __builtin_memcpy(&ib, &x.imm, 4);
-      if (f & kOpIbSlot) sa[k] = (int)(ib / MTGP_SLOT_BYTES);
-      if (f & kOpAxSlot) sb[k] = (int)((x.op & 0xffffffu) / MTGP_SLOT_BYTES);
-      far = far || sa[k] >= MTGP_MAX_DATA || sb[k] >= MTGP_MAX_DATA;
-      if (sa[k] >= 0 && sa[k] < MTGP_MAX_DATA) atomicMin(&fpos[sa[k]], 2 * i);
-      if (sb[k] >= 0 && sb[k] < MTGP_MAX_DATA) atomicMin(&fpos[sb[k]], 2 * i + 1);
+      int sa, sb;
+      slots(x, f, sa, sb);
+      far = far || sa >= MTGP_MAX_DATA || sb >= MTGP_MAX_DATA;
+      if (sa >= 0 && sa < MTGP_MAX_DATA) atomicMin(&fpos[sa], 2 * i);
+      if (sb >= 0 && sb < MTGP_MAX_DATA) atomicMin(&fpos[sb], 2 * i + 1);
     }
   }
   __syncthreads();
@@ -3744,19 +3749,21 @@ __device__ __forceinline__ void flat_jit_size_wave_lds(const MtgpInstr* prog, in
   const int npre = __popcll(pre_mask);
   int words = 0, sub = 0, carry = 0, rc = 0;
   bool failed = false;
-#pragma unroll
-  for (int k = 0; k < KI; ++k) {
+  for (int k = 0; k * kWave < n_wave; ++k) {
     const int i = k * kWave + lane;
     const bool in = i < n;
     int d = 0, e = 0;
     if (in) {
-      const uint32_t code = prog[i].op >> MTGP_OP_SHIFT;
+      const MtgpInstr x = prog[i];
+      const uint32_t code = x.op >> MTGP_OP_SHIFT;
       const uint32_t f = code < 64u ? T.flags[code] : 0u;
+      int sa, sb;
+      slots(x, f, sa, sb);
       if (!(f & kOpValid)) e = mtgp::kJitErrOpcode;
       d = (f & kOpPush) ? 1 : ((f & kOpPop) ? -1 : 0);
       words += code < 64u ? T.words[code] : 0;
-      if (sa[k] >= 0 && sa[k] < MTGP_MAX_DATA && !((pre_mask >> sa[k]) & 1ull)) words += 3;
-      if (sb[k] >= 0 && sb[k] < MTGP_MAX_DATA && !((pre_mask >> sb[k]) & 1ull)) words += 3;
+      if (sa >= 0 && sa < MTGP_MAX_DATA && !((pre_mask >> sa) & 1ull)) words += 3;
+      if (sb >= 0 && sb < MTGP_MAX_DATA && !((pre_mask >> sb) & 1ull)) words += 3;
       sub += code < 64u ? T.sub[code] : 0;
     }
     int incl = d;
@@ -4041,13 +4048,16 @@ constexpr long kResidentWaves = 8192;
 
 // Flatten, one WAVE per (individual, program spec): lane l owns rows l, l + 64, ... (NMAX / 64 per
 // lane), loaded with one coalesced 1-KB read per 64 rows.  The same two passes as k_flatten, but
-// level-synchronous over the tree instead of serial over the rows:
-//   pass 1: a row resolves (record, lengths, folded constant; mtgp_flatten_uniform.h) in the first
-//     round after its operand rows (j < i) have resolved -- rounds = the height of the dependency
-//     DAG, not N;
-//   pass 2: a reached row emits its word at the postorder position its parent assigned and
-//     assigns its children's -- rounds = the tree height.  A row reached twice (LDS atomic reach
-//     counter; only in arbitrary arrays) leaves the program to k_flatten_serial.
+// parallel over the rows instead of serial:
+//   pass 1: a row resolves (record, lengths, folded constant; mtgp_flatten_uniform.h u_resolve_op)
+//     in the first round after its operand rows (j < i) have resolved -- rounds = the height of
+//     the dependency DAG, not N;
+//   pass 2: the postorder position of a node is a sum over its path to the root, so every non-leaf
+//     row links its non-leaf operand rows to itself (u_claim), each row then adds up its own path
+//     (u_walk: one LDS read per level, no barrier between levels) and writes its word (u_emit_node)
+//     -- three phases whatever the height.  A row linked twice (LDS atomic counter; only in
+//     arbitrary arrays) needs its code once per path: lane 0 walks that program from the root
+//     (u_serial_walk, frames in the LDS table), so no second kernel has to look for such programs.
 // The tables are per wave in LDS (24 B per row), so the occupancy no longer falls with N (the
 // lane-per-tree kernel needs 16 B x N per LANE).  Output = k_flatten's word for word.
 // (8 waves per SIMD: the kernel is latency-bound -- one wave walks a tree level by level through
@@ -4121,25 +4131,6 @@ k_flatten_wave(const float* __restrict__ pop, int P, int T, int N,
 #pragma unroll
       for (int k = 0; k < RPL; ++k) cnt_others += __popcll(seg_ballot(xo[t][k] != 0.0f));
   }
-  auto operand = [&](int jj, int i, uint32_t& w, ULeaf& lf, int& len, int& flen, bool& leaf) {
-    if (jj < i) {
-      w = S.w[jj];
-      const uint32_t ln = S.len[jj];
-      len = (int)(ln & 0xffffu);
-      flen = (int)(ln >> 16);
-      lf.isc = u_isc(w);
-      lf.v = S.cv[jj];
-      lf.slot = u_slot(w);
-      leaf = u_leaf(w);
-    } else {
-      w = u_pack(K_CONST, 0, 0, 1, 1, 0);
-      lf.isc = true;
-      lf.v = S.val[jj];
-      lf.slot = 0;
-      len = flen = 1;
-      leaf = true;
-    }
-  };
   // ---- pass 1, round 0: leaves and empty rows resolve at once; operator rows note their operands
   int fnr[RPL], ja[RPL], jb[RPL];
   bool done[RPL];
@@ -4194,42 +4185,7 @@ k_flatten_wave(const float* __restrict__ pop, int P, int T, int N,
 #pragma unroll
     for (int k = 0; k < RPL; ++k) {
       if (!ready[k]) continue;
-      const int i = k * LP + lane;
-      const int fn = fnr[k], ar = fn_arity(fn);
-      uint32_t kind = ar == 1 ? K_UNARY : K_BINARY, isc = 1, afirst = 1, need = 0;
-      int len = 1, flen = 1;
-      float cv = 0.0f;
-      uint32_t wa, wb = 0;
-      ULeaf la, lb;
-      lb.isc = true; lb.v = 0.0f; lb.slot = 0;
-      int lena, flena, lenb = 1, flenb = 1;
-      bool leafa, leafb = true;
-      operand(ja[k], i, wa, la, lena, flena, leafa);
-      if (ar == 2) operand(jb[k], i, wb, lb, lenb, flenb, leafb);
-      if (la.isc && lb.isc) {  // constant subtree: folded with the kernel's fp32 primitives
-        cv = apply_fn(fn, la.v, ar == 1 ? 0.0f : lb.v);
-      } else {
-        isc = 0;
-        if (ar == 1) {
-          if (leafa) { len = 2; flen = unary_fuses(fn) ? 1 : 2; }
-          else { len = lena + 1; flen = flena + 1; need = u_need(wa); }
-        } else if (leafa && leafb) {
-          len = 2; flen = 1;
-        } else if (leafb) {
-          len = lena + 1; flen = flena + 1; need = u_need(wa);
-        } else if (leafa) {
-          len = lenb + 1; flen = flenb + 1; need = u_need(wb);
-        } else {
-          const uint32_t pa = u_need(wa), qb = u_need(wb);
-          len = lena + lenb + 1;
-          flen = flena + flenb + 1;
-          if (pa >= qb) { afirst = 1; need = pa > qb + 1 ? pa : qb + 1; }
-          else { afirst = 0; need = qb > pa + 1 ? qb : pa + 1; }
-        }
-      }
-      S.w[i] = u_pack(kind, (uint32_t)fn, 0, isc, afirst, need > 31u ? 31u : need);
-      S.len[i] = (uint32_t)(len > 65535 ? 65535 : len) | (uint32_t)(flen > 65535 ? 65535 : flen) << 16;
-      S.cv[i] = cv;
+      u_resolve_op(S, k * LP + lane, fnr[k], ja[k], jb[k]);
     }
     __syncthreads();  // every read of this round's flags precedes the new ones
 #pragma unroll
@@ -4245,9 +4201,11 @@ k_flatten_wave(const float* __restrict__ pop, int P, int T, int N,
   if ((int)u_need(wr) > MTGP_STACK_MAX) n = -MTGP_ERR_STACK;
   else if ((int)(lr & 0xffffu) > cap) n = -MTGP_ERR_PROG_TOO_LONG;
   else n = (int)(lr >> 16);
-  // ---- pass 2: postorder positions top-down, one word per reached node, one level per round
-  // (the walk's barriers stay in wave-uniform control flow: with two programs per wave, a program
-  // that does not walk takes part with no row reached)
+  // ---- pass 2 (mtgp_flatten_uniform.h "closed form"): every non-leaf row links its non-leaf operand
+  // rows to itself, then each row sums the links on its own path to the root and, if it gets
+  // there, writes its word -- three LDS phases whatever the tree's height (was one level per
+  // round).  (The barriers stay in wave-uniform control flow: with two programs per wave, a
+  // program that does not walk takes part with no row linked.)
   bool shared = false;
   const bool walk = n > 0 && !u_leaf(wr);
   if (n > 0 && u_leaf(wr) && lane == 0) {  // the whole tree is one leaf
@@ -4255,106 +4213,72 @@ k_flatten_wave(const float* __restrict__ pop, int P, int T, int N,
     x.isc = u_isc(wr); x.v = S.cv[N - 1]; x.slot = u_slot(wr);
     out[0] = S.prog[0] = u_load(x, false);
   }
-  {
-    if (LP == kWave ? walk : wave_any(walk)) {
-      __syncthreads();
+  auto emit = [&](int at, const MtgpInstr& v) {
+    if (at >= L) return;  // (never: the positions add up to the root's length, which is below L)
+    out[at] = v;
+    if (at < NMAX + 8) S.prog[at] = v;  // (beyond it only with a shared row: sized from `out`)
+  };
+  if (LP == kWave ? walk : wave_any(walk)) {
+    __syncthreads();
 #pragma unroll
-      for (int k = 0; k < RPL; ++k) S.flag[k * LP + lane] = 0u;
-      __syncthreads();
-      if (walk && lane == 0) {
-        S.flag[N - 1] = 1u;
-        S.pos[N - 1] = 0;
-      }
-      bool emitted[RPL];
+    for (int k = 0; k < RPL; ++k) {
+      S.flag[k * LP + lane] = 0u;
+      S.pos[k * LP + lane] = (int32_t)kULinkNone;
+    }
+    __syncthreads();
+    bool node[RPL];  // an operator row that did not fold: the rows that own a word
 #pragma unroll
-      for (int k = 0; k < RPL; ++k) emitted[k] = false;
-      for (;;) {
-        __syncthreads();
-        bool go[RPL], any = false;
+    for (int k = 0; k < RPL; ++k) {
+      const int i = k * LP + lane;
+      node[k] = walk && fnr[k] >= 0 && !u_isc(S.w[i]);
+      if (node[k]) u_claim(S, i, ja[k], jb[k], [&](int c) { atomicAdd(&S.flag[c], 1u); });
+    }
+    __syncthreads();
+    // a row linked twice (arbitrary arrays only) holds one of its links: the serial walk below
 #pragma unroll
-        for (int k = 0; k < RPL; ++k) {
-          const int i = k * LP + lane;
-          go[k] = i < N && !emitted[k] && S.flag[i] != 0u;
-          any = any || go[k];
-        }
-        if (!wave_any(any)) break;
-        __syncthreads();  // every row's go decision precedes this round's visits
+    for (int k = 0; k < RPL; ++k) shared = shared || S.flag[k * LP + lane] > 1u;
+    shared = seg_ballot(shared) != 0ull;
+    if (!shared) {
 #pragma unroll
-        for (int k = 0; k < RPL; ++k) {
-          if (!go[k]) continue;
-          emitted[k] = true;
-          const int i = k * LP + lane;
-          const uint32_t w = S.w[i];
-          const int pp = S.pos[i], pos = pp & 0xffff;
-          const bool push = (pp >> 16) != 0;
-          const int fn = (int)u_fn(w);
-          uint32_t wa, wb;
-          ULeaf la, lb;
-          int lena, flena, lenb = 1, flenb = 1;
-          bool leafa, leafb = true;
-          const int ca = ja[k];
-          operand(ca, i, wa, la, lena, flena, leafa);
-          const int cb = u_kind(w) == K_BINARY ? jb[k] : 0;
-          if (u_kind(w) == K_BINARY) operand(cb, i, wb, lb, lenb, flenb, leafb);
-          auto visit = [&](int c, int cpos, bool cpush) {
-            S.pos[c] = cpos | (cpush ? 1 << 16 : 0);
-            shared = shared || atomicAdd(&S.flag[c], 1u) != 0u;  // a sub-DAG reached twice
-          };
-          MtgpInstr x;
-          auto emit = [&](int at, const MtgpInstr& v) {
-            out[at] = v;
-            S.prog[at] = v;
-          };
-          if (u_kind(w) == K_UNARY) {
-            const MtgpInstr un = u_instr(mtgp::unary_op(fn), 0, 0.0f);
-            if (leafa) {
-              MtgpInstr w2[2];
-              const int nw = u_unary_leaf(fn, la, push, w2);
-              emit(pos, w2[0]);  // (nw is 1 or 2; no dynamic index into w2, which would put it in scratch)
-              if (nw > 1) emit(pos + 1, w2[1]);
-            } else { visit(ca, pos, push); emit(pos + flena, un); }
-          } else if (leafa && leafb) {
-            fuse_pair(u_load(la, push), u_op_leaf(fn, 0, lb), &x);
-            emit(pos, x);
-          } else if (leafb) {
-            visit(ca, pos, push);
-            emit(pos + flena, u_op_leaf(fn, 0, lb));
-          } else if (leafa) {
-            visit(cb, pos, push);
-            emit(pos + flenb, u_op_leaf(fn, 1, la));
-          } else {
-            const bool af = u_afirst(w) != 0;
-            const int f1 = af ? flena : flenb, f2 = af ? flenb : flena;
-            visit(af ? ca : cb, pos, push);
-            visit(af ? cb : ca, pos + f1, true);
-            emit(pos + f1 + f2, u_op_stack(fn, af ? 1 : 0));
-          }
-        }
+      for (int k = 0; k < RPL; ++k) {
+        if (!node[k]) continue;
+        const int i = k * LP + lane;
+        const int pp = u_walk(S, i, N - 1);
+        if (pp >= 0) u_emit_node(S, i, ja[k], jb[k], pp & 0xffff, (pp >> 16) != 0, emit, [](int, int, bool) {});
       }
     }
+    if (wave_any(shared)) {  // one lane walks the program from the root (u_serial_walk)
+      __syncthreads();       // (every link read precedes the frames, which reuse the table)
+      if (shared && lane == 0) {
+        const bool ok = u_serial_walk(S, N - 1, cap, NMAX, emit, [&](int i, int& ca, int& cb) {
+          const float4 r = tr[i];
+          ca = norm_index(r.y, N);
+          cb = norm_index(r.z, N);
+        });
+        if (!ok) n = -MTGP_ERR_PROG_TOO_LONG;
+      }
+      n = __shfl(n, 0, LP);
+    }
   }
-  shared = seg_ballot(shared) != 0ull;
-  __syncthreads();  // every lane's program words (LDS copy) precede the END and the JIT sizing
+  __syncthreads();  // every lane's program words precede the END and the JIT sizing
   if (lane == 0) {
-    if (shared) {  // arbitrary arrays only: the serial walk duplicates the shared subtree
-      len_out[pj] = 0;
-      status_out[pj] = kFlatSerial;
-    } else {
-      MtgpInstr e;
-      e.op = (uint32_t)MTGP_OP_END << MTGP_OP_SHIFT;
-      e.imm = 0.0f;
-      out[n > 0 ? n : 0] = e;
-      S.prog[n > 0 ? n : 0] = e;
-      len_out[pj] = n > 0 ? n : 0;
-      status_out[pj] = n > 0 ? 0 : -n;
-    }
+    MtgpInstr e;
+    e.op = (uint32_t)MTGP_OP_END << MTGP_OP_SHIFT;
+    e.imm = 0.0f;
+    emit(n > 0 ? n : 0, e);
+    len_out[pj] = n > 0 ? n : 0;
+    status_out[pj] = n > 0 ? 0 : -n;
   }
-  if (!shared && (jit_words_out || jit_cost_out)) {  // (shared: wave-uniform)
-    constexpr int KI = (2 * NMAX + 8 + LP - 1) / LP;
+  if (jit_words_out || jit_cost_out) {
+    // the program as written is in LDS, unless a shared row made it longer than the LDS copy
+    const bool big = n > NMAX + 7;
+    if (wave_any(big)) __syncthreads();  // (lane 0's words in `out` precede the other lanes' reads)
     if (jit_mode == kJitModeRegs) {
-      flat_jit_size_wave<KI, LP>(S.prog, n, optab, jit_words_out, jit_cost_out, pj, lane);
+      if (wave_any(big)) flat_jit_size_wave<LP>(out, n, optab, jit_words_out, jit_cost_out, pj, lane);
+      else flat_jit_size_wave<LP>(S.prog, n, optab, jit_words_out, jit_cost_out, pj, lane);
     } else if constexpr (LP == kWave) {  // (two programs per wave: register mode only, mtgp_flatten_ex)
-      flat_jit_size_wave_lds<KI>(S.prog, n, optab, jit_words_out, jit_cost_out, pj, lane, s_fpos);
+      if (big) flat_jit_size_wave_lds(out, n, optab, jit_words_out, jit_cost_out, pj, lane, s_fpos);
+      else flat_jit_size_wave_lds(S.prog, n, optab, jit_words_out, jit_cost_out, pj, lane, s_fpos);
     }
   }
   // node count (gp.py:424 parsimony).  Few trees (T <= kFlatDirectTrees): the individual's first
@@ -5991,9 +5915,11 @@ int mtgp_flatten_ex(const float* population, int32_t P, int32_t T, int32_t N, co
     else if (tp >= 32) MTGP_FLAT_ONE(NM, 32);                                                               \
     else if (tp >= 16) MTGP_FLAT_ONE(NM, 16);                                                               \
     else MTGP_FLAT_ONE(NM, 8);                                                                              \
-    hipLaunchKernelGGL(k_flatten_serial<NM>, dim3((unsigned)(total < 256 * 64 ? (total + 63) / 64 : 256)), \
-                       dim3(64), 0, s, population, P, T, N, libv, specs, n_prog, L, prog_out, len_out,     \
-                       status_out, jit_words_out, jit_cost_out, jit_mode);                                  \
+    /* the wave kernel finishes every program itself; the lane kernel leaves shared rows to this one */    \
+    if (!wave_mode)                                                                                         \
+      hipLaunchKernelGGL(k_flatten_serial<NM>, dim3((unsigned)(total < 256 * 64 ? (total + 63) / 64 : 256)), \
+                         dim3(64), 0, s, population, P, T, N, libv, specs, n_prog, L, prog_out, len_out,   \
+                         status_out, jit_words_out, jit_cost_out, jit_mode);                                \
   } while (0)
   if (N <= 64) MTGP_FLAT_LAUNCH(64);
   else if (N <= 128) MTGP_FLAT_LAUNCH(128);
