@@ -435,6 +435,51 @@ int mtgp_eval_rk4_jit(const MtgpModel* model, const MtgpInstr* prog, const int32
                       const MtgpRollouts* rollouts, const MtgpOutputs* out, const MtgpJitCode* jit,
                       void* stream);
 
+/* -------------------------------------------------------- pointwise regression */
+/* Static symbolic regression y = f(x) on a table of M samples (no ODE): candidate p has n_out
+ * programs (n_prog >= n_out; programs 0 .. n_out-1 are its outputs) reading the inputs x0 ..
+ * x{n_var-1} as data slots 0 .. n_var-1.  One fused kernel evaluates the programs at every point,
+ * forms the squared error and reduces it in registers; only fitness[P] (and, on request, the
+ * predictions) leaves the CU.  The f32 order is the spec (DESIGN.md "Pointwise evaluator"):
+ *   sq_m = e_0 e_0, then + e_d e_d for d = 1 .. n_out-1, with e_d = f_d(x_m) - Y[m, d];
+ *   a wave covers a span of MTGP_PW_SPAN points; its lane l adds sq_m of the points span + l,
+ *   span + l + 64, ... in ascending order starting from the first; the 64 lane sums (+0 for a lane
+ *   without a point) are combined by the xor butterfly (lane ^ 1, ^ 2, ... ^ 32);
+ *   W = ceil(M / MTGP_PW_SPAN) span sums are combined pairwise in span order (zeros up to the next
+ *   power of two); then / (float)M, a non-finite value -> max_fitness, clip to [0, max_fitness],
+ *   + parsimony * nodes[p].
+ * W depends on M alone, so results do not depend on P, the schedule or the device.
+ * Buffers are the caller's, on the device, 16-byte aligned where noted; nothing is allocated. */
+#define MTGP_PW_SPAN 4096
+#define MTGP_PW_MAX_VAR 8 /* the register-data JIT's data vector v0-v7 */
+#define MTGP_PW_MAX_OUT 4 /* one role chain (v26..v29) */
+typedef struct {
+  const float* xt;      /* [n_var][ld] inputs, transposed (a chunk load is coalesced); 16-byte aligned */
+  const float* yt;      /* [n_out][ld] targets, transposed; 16-byte aligned                           */
+  int32_t M;            /* points, >= 1                                                                */
+  int32_t ld;           /* row stride of xt / yt in floats: a multiple of 4, >= M (padding is read,    */
+                        /* never used)                                                                 */
+  int32_t n_var;        /* 1 .. MTGP_PW_MAX_VAR                                                        */
+  int32_t n_out;        /* 1 .. MTGP_PW_MAX_OUT                                                        */
+  float max_fitness;
+  float parsimony;
+  const int32_t* nodes; /* [P] node counts (mtgp_flatten)                                              */
+  const int32_t* order; /* optional [P] schedule for lane set 64 (mtgp_schedule: longest first)        */
+  float* fitness;       /* [P]                                                                         */
+  float* partials;      /* [P, W] scratch, needed when M > MTGP_PW_SPAN                                */
+  float* pred;          /* optional [P, n_out, M] predictions                                          */
+} MtgpPointwise;
+
+/* Interpreter only. */
+int mtgp_eval_pointwise(const MtgpPointwise* pw, const MtgpInstr* prog, const int32_t* plen, int32_t n_prog,
+                        int32_t L, int32_t P, void* stream);
+/* With JIT code built in MTGP_JIT_MODE_REGS for lane set 64 and pw->order, its chain either none
+ * or programs 0 .. n_out-1 as one role chain (next = bits 0 .. n_out-2); jit NULL or without code:
+ * the interpreter.  The kernel interprets too when `info` says the code is unusable.  Identical
+ * bits on every path. */
+int mtgp_eval_pointwise_jit(const MtgpPointwise* pw, const MtgpInstr* prog, const int32_t* plen, int32_t n_prog,
+                            int32_t L, int32_t P, const MtgpJitCode* jit, void* stream);
+
 /* ------------------------------------------------- coefficient optimisation */
 /* Loss and forward-mode gradient of the SR fitness w.r.t. K parameters per individual (ABI v11),
  * the value_and_grad of GeneticProgramming.epoch (gp.py:435-452, vmap_gradients gp.py:253).

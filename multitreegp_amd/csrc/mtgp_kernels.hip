@@ -45,7 +45,8 @@
 // them recompiles this unit only, scripts/build_ab.py), MTGP_TU=8 the SR kernels, MTGP_TU=9 the
 // runtime-state-size Dopri5 control kernels (state_size 4 .. 16, round 6), MTGP_TU=10 the
 // fixed-step Acrobot kernels of the static policy (the C2 hot kernel; out of unit 7 since round 8,
-// which compiles unit 7 without the SLP vectorizer -- that costs the static loop 3 %), behind one
+// which compiles unit 7 without the SLP vectorizer -- that costs the static loop 3 %), MTGP_TU=11
+// the pointwise regression kernels (k_pointwise, k_pointwise_mean), behind one
 // hidden C++ entry each.  Without MTGP_TU it is one monolithic TU.
 #ifdef MTGP_TU
 #define MTGP_TU_IS(n) (MTGP_TU == (n))
@@ -63,6 +64,7 @@
 #define MTGP_TU_SR MTGP_TU_IS(8)
 #define MTGP_TU_DP_RT MTGP_TU_IS(9)
 #define MTGP_TU_ACRO_STATIC MTGP_TU_IS(10)
+#define MTGP_TU_POINTWISE MTGP_TU_IS(11)
 
 namespace {
 
@@ -3548,6 +3550,194 @@ __global__ void __launch_bounds__(512) k_sr_wide_dopri5(KArgs A) {
   if (w == 0) finish_group(A, Ln, tot / (float)S);
 }
 
+// --------------------------------------------------------------------------------------
+// Pointwise regression (mtgp.h MtgpPointwise): y = f(x) on a table of M samples, fused map and
+// reduce.  Lanes are data points; one wave runs one individual on one span of MTGP_PW_SPAN points,
+// 64 points per chunk, and keeps the squared-error sum in a register.  The kPwWaves waves of a
+// workgroup hold kPwWaves individuals (consecutive schedule slots) on the SAME span, so the span's
+// X and Y rows cross HBM / L2 once per workgroup: every thread fetches 16 bytes per row piece
+// (global_load_dwordx4 from the transposed, padded rows) of the NEXT tile of kPwTile points into
+// registers before the waves evaluate the current tile from LDS, and stores them into the other
+// LDS buffer afterwards (one barrier per tile).  A tile row is kPwTile consecutive floats, so a
+// wave reads its data slot k of chunk c as one conflict-free 64-lane column.  The n_out programs
+// are one role chain (one s_swappc_b64 per chunk, results in v26..) or, unchained, one call each;
+// the interpreter runs them when the code is unusable and for lanes flagged in s[32:33].
+constexpr int kPwWaves = 8;
+constexpr int kPwTile = 4 * kWave;
+constexpr int kPwRows = MTGP_PW_MAX_VAR + MTGP_PW_MAX_OUT;
+constexpr int kPwVecs = (kPwRows * kPwTile / 4 + kPwWaves * kWave - 1) / (kPwWaves * kWave);  // float4 per thread and tile
+
+struct PwArgs {
+  MtgpPointwise pw;
+  const MtgpInstr* prog;
+  int32_t n_prog, L, P;
+  int32_t W;                // spans per individual: ceil(M / MTGP_PW_SPAN)
+  uint64_t jit_base;        // as KArgs: the code buffer, the per-(wave, program) unit offsets, the plan's info
+  const uint32_t* jit_off;
+  const int32_t* jit_info;
+  uint64_t jit_cap;
+  int32_t chained;          // programs 0 .. n_out-1 are one role chain
+};
+
+// sum / M, a non-finite mean -> max_fitness, clip, parsimony: the epilogue of both reductions
+__device__ __forceinline__ float pw_finish(const MtgpPointwise& pw, float sum, int p) {
+  const float mx = pw.max_fitness;
+  float mean = sum / (float)pw.M;
+  if (!mtgp_isfinite(mean)) mean = mx;
+  mean = mean < 0.0f ? 0.0f : (mean > mx ? mx : mean);
+  return mean + pw.parsimony * (float)pw.nodes[p];
+}
+
+// the n_out programs of individual p on this wave's chunk: data d[] -> f[]
+template <bool JIT>
+__device__ __forceinline__ void pw_run(const PwArgs& A, int p, int no, bool jok, uint32_t jtab, int lane,
+                                       const float (&d)[kDMax], float* dcol, float* st,
+                                       float (&f)[MTGP_PW_MAX_OUT]) {
+  uint64_t fl = 0;
+  const bool coded = JIT && jok;
+  if (coded) {
+    if (A.chained) {
+      const uint32_t off = (uint32_t)__builtin_amdgcn_readlane((int)jtab, 0);
+      const ChainOut r = jit_call_chain(A.jit_base + off, d, fl, 0);
+#pragma unroll
+      for (int j = 0; j < MTGP_PW_MAX_OUT; ++j) f[j] = r.v[j];
+    } else {
+#pragma unroll 1
+      for (int q = 0; q < no; ++q) {
+        const uint32_t off = (uint32_t)__builtin_amdgcn_readlane((int)jtab, q);
+        const float v = jit_call(A.jit_base + off, d, fl);
+#pragma unroll
+        for (int j = 0; j < MTGP_PW_MAX_OUT; ++j) f[j] = (q == j) ? v : f[j];
+      }
+    }
+    if (__builtin_expect(fl == 0, 1)) return;
+  }
+  // the interpreter: every lane without usable code, else the lanes that need the slow sin/cos reduction
+  const bool mine = !coded || ((fl >> lane) & 1ull) != 0;
+#pragma unroll
+  for (int k = 0; k < kDMax; ++k) dcol[k * kWave] = d[k];
+#pragma unroll 1
+  for (int q = 0; q < no; ++q) {
+    const float v = run_prog(A.prog + ((size_t)p * A.n_prog + q) * A.L, dcol, st);
+#pragma unroll
+    for (int j = 0; j < MTGP_PW_MAX_OUT; ++j) f[j] = (q == j && mine) ? v : f[j];
+  }
+}
+
+template <bool JIT>
+__global__ void __launch_bounds__(kPwWaves * kWave) k_pointwise(PwArgs A) {
+  __shared__ float4 tile[2][kPwRows * kPwTile / 4];
+  __shared__ float work[kPwWaves][kLdsWaveWords];  // the interpreter's data and stack columns
+  const int wave = uni(threadIdx.x >> 6), lane = threadIdx.x & 63;
+  const int W = A.W;
+  const int ig = (int)blockIdx.x / W, sp = (int)blockIdx.x - ig * W;
+  const int q = ig * kPwWaves + wave;
+  const bool live = q < A.P;  // (a wave without an individual still stages its share of the tiles)
+  const int p = live ? uni(A.pw.order ? A.pw.order[q] : q) : 0;
+  const int M = A.pw.M, ld = A.pw.ld, nv = A.pw.n_var, no = A.pw.n_out;
+  const int m0 = sp * MTGP_PW_SPAN;
+  const int span = M - m0 < MTGP_PW_SPAN ? M - m0 : MTGP_PW_SPAN;
+  const int nt = (span + kPwTile - 1) / kPwTile;
+  const int nvec = (nv + no) * (kPwTile / 4);  // 16-byte pieces of a tile: row r = v / 64, points 4 (v % 64) ..
+  bool jok = false;
+  uint32_t jtab = 0;
+  if (JIT) {
+    asm volatile("s_icache_inv");  // the JIT code was written by an earlier kernel
+    jok = true;
+    if (A.jit_info) jok = uni((int)(A.jit_info[0] == 0 && (uint64_t)(uint32_t)A.jit_info[1] <= A.jit_cap)) != 0;
+    if (live && lane < no) jtab = A.jit_off[(size_t)q * A.n_prog + lane];
+  }
+  auto fetch = [&](int t, float4 (&r)[kPwVecs]) {
+#pragma unroll
+    for (int k = 0; k < kPwVecs; ++k) {
+      const int v = (int)threadIdx.x + k * kPwWaves * kWave;
+      r[k] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+      if (v >= nvec) continue;
+      const int row = v / (kPwTile / 4), pm = m0 + t * kPwTile + (v % (kPwTile / 4)) * 4;
+      if (pm >= ld) continue;  // (ld is a multiple of 4: the piece lies inside the row or past it)
+      const float* src = row < nv ? A.pw.xt + (size_t)row * ld : A.pw.yt + (size_t)(row - nv) * ld;
+      r[k] = *reinterpret_cast<const float4*>(src + pm);
+    }
+  };
+  auto stash = [&](int b, const float4 (&r)[kPwVecs]) {
+#pragma unroll
+    for (int k = 0; k < kPwVecs; ++k) {
+      const int v = (int)threadIdx.x + k * kPwWaves * kWave;
+      if (v < nvec) tile[b][v] = r[k];
+    }
+  };
+  float4 nx[kPwVecs];
+  fetch(0, nx);
+  stash(0, nx);
+  __syncthreads();
+  float* dcol = &work[wave][lane];
+  float* st = &work[wave][kDMax * kWave + lane];
+  float acc = 0.0f;
+  for (int t = 0; t < nt; ++t) {
+    const bool more = t + 1 < nt;
+    if (more) fetch(t + 1, nx);  // in flight while this tile is evaluated
+    if (live) {
+      const float* tl = reinterpret_cast<const float*>(tile[t & 1]);
+      const int left = span - t * kPwTile;
+      const int nc = left >= kPwTile ? kPwTile / kWave : (left + kWave - 1) / kWave;
+#pragma unroll 1
+      for (int c = 0; c < nc; ++c) {
+        const int off = c * kWave + lane;
+        const int m = m0 + t * kPwTile + off;
+        const bool valid = m < M;
+        float d[kDMax], f[MTGP_PW_MAX_OUT];
+#pragma unroll
+        for (int k = 0; k < kDMax; ++k) d[k] = k < nv ? tl[k * kPwTile + off] : 0.0f;
+#pragma unroll
+        for (int j = 0; j < MTGP_PW_MAX_OUT; ++j) f[j] = 0.0f;
+        pw_run<JIT>(A, p, no, jok, jtab, lane, d, dcol, st, f);
+        float sq = 0.0f;
+#pragma unroll
+        for (int j = 0; j < MTGP_PW_MAX_OUT; ++j) {
+          if (j < no) {
+            const float e = f[j] - tl[(nv + j) * kPwTile + off];
+            sq = (j == 0) ? e * e : sq + e * e;
+          }
+        }
+        if (valid) acc = (t == 0 && c == 0) ? sq : acc + sq;  // (a lane's first point lies in the span's first chunk)
+        if (A.pw.pred && valid) {
+#pragma unroll
+          for (int j = 0; j < MTGP_PW_MAX_OUT; ++j)
+            if (j < no) A.pw.pred[((size_t)p * no + j) * M + m] = f[j];
+        }
+      }
+    }
+    if (more) stash((t + 1) & 1, nx);
+    __syncthreads();
+  }
+  if (!live) return;
+  float v = acc;  // (+0 in a lane without a point)
+  for (int w = 1; w < kWave; w <<= 1) v = v + __shfl_xor(v, w, kWave);
+  if (lane != 0) return;
+  if (W > 1) A.pw.partials[(size_t)p * W + sp] = v;
+  else A.pw.fitness[p] = pw_finish(A.pw, v, p);
+}
+
+#if MTGP_TU_POINTWISE
+// Fitness of individuals whose M points span several waves: the W span sums combined pairwise in
+// span order (zeros up to the next power of two; a binary-counter stack as in k_rollout_mean), then
+// pw_finish.  One thread per individual.
+__global__ void __launch_bounds__(256) k_pointwise_mean(MtgpPointwise pw, int P, int W) {
+  const int p = blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= P) return;
+  int np2 = 1, top = 0;
+  while (np2 < W) { np2 <<= 1; ++top; }
+  float cst[32];
+  for (int c = 0; c < np2; ++c) {
+    float x = c < W ? pw.partials[(size_t)p * W + c] : 0.0f;
+    int lvl = 0;
+    for (; (c >> lvl) & 1; ++lvl) x = cst[lvl] + x;
+    cst[lvl] = x;
+  }
+  pw.fitness[p] = pw_finish(pw, cst[top], p);
+}
+#endif
+
 #if MTGP_TU_MAIN
 // --------------------------------------------------------------------------------------
 // tree_evaluator plugin (gp.py:390-401): every program on M shared data vectors.
@@ -5531,6 +5721,20 @@ int mtgp_tu_launch_sr(const void* A_, const MtgpModel* model, const MtgpLaunchCt
 }
 #endif
 
+// the pointwise regression kernels (MTGP_TU 11): one wave per (individual, span), then the span sums
+MTGP_HIDDEN int mtgp_tu_launch_pointwise(const void* A, bool jit, hipStream_t s);
+#if MTGP_TU_POINTWISE
+int mtgp_tu_launch_pointwise(const void* A_, bool jit, hipStream_t s) {
+  const PwArgs& A = *(const PwArgs*)A_;
+  const dim3 grid((unsigned)(((long)A.P + kPwWaves - 1) / kPwWaves * A.W)), block(kPwWaves * kWave);
+  return launch_checked([&] {
+    mtgp::with_flag(jit, [&](auto J) { hipLaunchKernelGGL((k_pointwise<J()>), grid, block, 0, s, A); });
+    if (A.W > 1)
+      hipLaunchKernelGGL(k_pointwise_mean, dim3((unsigned)((A.P + 255) / 256)), dim3(256), 0, s, A.pw, A.P, A.W);
+  });
+}
+#endif
+
 #if MTGP_TU_MAIN
 namespace {
 
@@ -6138,6 +6342,49 @@ int mtgp_eval_rk4_jit(const MtgpModel* model, const MtgpInstr* prog, const int32
   hipLaunchKernelGGL(k_rollout_mean, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, s, out->rollout_fitness, P,
                      rollouts->R, model->max_fitness, model->parsimony, nodes, out->fitness);
   return hipGetLastError() == hipSuccess ? MTGP_OK : MTGP_ERR_LAUNCH;
+}
+
+int mtgp_eval_pointwise(const MtgpPointwise* pw, const MtgpInstr* prog, const int32_t* plen, int32_t n_prog,
+                        int32_t L, int32_t P, void* stream) {
+  return mtgp_eval_pointwise_jit(pw, prog, plen, n_prog, L, P, nullptr, stream);
+}
+
+int mtgp_eval_pointwise_jit(const MtgpPointwise* pw, const MtgpInstr* prog, const int32_t* plen, int32_t n_prog,
+                            int32_t L, int32_t P, const MtgpJitCode* jitc, void* stream) {
+  if (!pw || !prog || !plen || !pw->xt || !pw->yt || !pw->nodes || !pw->fitness) return MTGP_ERR_ARG;
+  if (P < 0 || L <= 0 || (L & 3) != 0 || n_prog <= 0 || n_prog > MTGP_MAX_PROGRAMS) return MTGP_ERR_ARG;
+  if (pw->n_var < 1 || pw->n_var > MTGP_PW_MAX_VAR || pw->n_out < 1 || pw->n_out > MTGP_PW_MAX_OUT ||
+      pw->n_out > n_prog)
+    return MTGP_ERR_ARG;
+  if (pw->M < 1 || pw->ld < pw->M || (pw->ld & 3) != 0) return MTGP_ERR_ARG;
+  if (((reinterpret_cast<uintptr_t>(pw->xt) | reinterpret_cast<uintptr_t>(pw->yt)) & 15u) != 0) return MTGP_ERR_ARG;
+  if (!(pw->max_fitness >= 0.0f)) return MTGP_ERR_ARG;
+  const int W = (int)(((long)pw->M + MTGP_PW_SPAN - 1) / MTGP_PW_SPAN);
+  if (W > 1 && !pw->partials) return MTGP_ERR_ARG;
+  if (((long)P + kPwWaves - 1) / kPwWaves * W > (long)INT32_MAX) return MTGP_ERR_ARG;
+  const bool jit = jitc && jitc->code && jitc->offsets;
+  int chained = 0;
+  if (jit) {  // no chain, or programs 0 .. n_out-1 as one
+    const MtgpJitChain& ch = jitc->chain;
+    const uint32_t want = pw->n_out >= 2 ? (1u << (pw->n_out - 1)) - 1u : 0u;
+    if (ch.cond != 0u || ch.store != 0u || ch.put != 0u || (ch.next != 0u && ch.next != want)) return MTGP_ERR_ARG;
+    chained = ch.next != 0u;
+  }
+  if (P == 0) return MTGP_OK;
+  PwArgs A;
+  A.pw = *pw;
+  A.prog = prog;
+  A.n_prog = n_prog;
+  A.L = L;
+  A.P = P;
+  A.W = W;
+  A.jit_base = jit ? (uint64_t)(uintptr_t)jitc->code : 0;
+  A.jit_off = jit ? jitc->offsets : nullptr;
+  A.jit_info = jit ? jitc->info : nullptr;
+  A.jit_cap = jit ? jitc->capacity : 0;
+  A.chained = chained;
+  hipStream_t s = (hipStream_t)stream;
+  return launch_timed([&] { return mtgp_tu_launch_pointwise(&A, jit, s); }, s);
 }
 
 }  // extern "C"

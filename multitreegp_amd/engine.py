@@ -210,6 +210,9 @@ class DeviceEngine:
         ch = nat.MtgpJitChain(0, 0, 0)
         if os.environ.get("MTGP_JIT_CHAIN", "1") == "0":
             return ch
+        if self.ff.model_id == nat.MODEL_POINTWISE:  # the n_out trees as one chain (mtgp_eval_pointwise_jit)
+            ch.next = (1 << (n_prog - 1)) - 1
+            return ch
         if self._jit_mode() == nat.JIT_MODE_LDS and self.ff.model_id != nat.MODEL_SR:
             return ch  # (the runtime-state-size control kernels call one unit per program)
         rc = self.native.mtgp_jit_chain(ctypes.byref(m), n_prog, ctypes.byref(ch))
@@ -258,7 +261,7 @@ class DeviceEngine:
             return self._data
         host = self.ff.prepare(data)
         dev = {}
-        for name in ("x0", "params", "targets", "ts", "ys_true", "obs_keys", "obs_w", "fit_kof"):
+        for name in ("x0", "params", "targets", "ts", "ys_true", "obs_keys", "obs_w", "fit_kof", "xt", "yt"):
             a = host.get(name)
             a = None if a is None else np.asarray(a)
             dev[name] = None if a is None or a.size == 0 else torch.from_numpy(np.ascontiguousarray(a)).to(self.device)
@@ -471,7 +474,10 @@ class DeviceEngine:
         buffer.  res["_traj_layout"] names the storage (nat.TRAJ_TIME_MAJOR / TRAJ_LANE_MAJOR):
         read the tensors through indexing or to_reference_layout, and never hand their
         data_ptr() to native code without checking it.
-        schedule: pair expensive with cheap individuals in each wave (results are identical)."""
+        schedule: pair expensive with cheap individuals in each wave (results are identical).
+        PointwiseEvaluator: fitness [P] and, with trajectories, pred [P, n_out, M]."""
+        if self.ff.model_id == nat.MODEL_POINTWISE:
+            return self._evaluate_pointwise(pop, data, trajectories, flattened, check, schedule)
         d = self.prepare_data(data)
         fl = flattened if flattened is not None else self.flatten(pop)
         P = pop.shape[0]
@@ -578,6 +584,43 @@ class DeviceEngine:
         if self._dp_frac is None or self._dp_evals % self.kDpProbeEvery == 0:
             return two
         return 0 if self._dp_frac < self.kDpOneLaunchFrac else two
+
+    def _evaluate_pointwise(self, pop: torch.Tensor, data, predictions: bool, flattened: Optional[Flattened],
+                            check: bool, schedule: bool) -> dict:
+        """PointwiseEvaluator: flatten, schedule and JIT build as for the ODE evaluators (lane set 64:
+        one individual per unit, the longest programs first), then mtgp_eval_pointwise_jit."""
+        d = self.prepare_data(data)
+        fl = flattened if flattened is not None else self.flatten(pop)
+        P, dev = pop.shape[0], self.device
+        order = self.schedule(fl, 64) if schedule and P > 1 else None
+        M, n_out = d["M"], d["n_out"]
+        W = (M + nat.PW_SPAN - 1) // nat.PW_SPAN
+        res = {"fitness": torch.empty((P,), dtype=torch.float32, device=dev)}
+        pw = nat.MtgpPointwise()
+        pw.xt, pw.yt, pw.M, pw.ld = d["xt_dev"].data_ptr(), d["yt_dev"].data_ptr(), M, d["ld"]
+        pw.n_var, pw.n_out = d["n_var"], n_out
+        pw.max_fitness, pw.parsimony = self.ff.max_fitness, self.parsimony
+        pw.nodes, pw.order, pw.fitness = fl.nodes.data_ptr(), _ptr(order), res["fitness"].data_ptr()
+        if W > 1:  # span sums of the individuals whose points take several waves
+            res["_partials"] = torch.empty((P, W), dtype=torch.float32, device=dev)
+            pw.partials = res["_partials"].data_ptr()
+        if predictions:
+            res["pred"] = torch.empty((P, n_out, M), dtype=torch.float32, device=dev)
+            pw.pred = res["pred"].data_ptr()
+        jit = self.jit_build(fl, None, 64, order)
+        jc = nat.MtgpJitCode()
+        if jit is not None:
+            jc.code, jc.offsets, jc.info, jc.capacity = jit[0], jit[1].data_ptr(), jit[2].data_ptr(), jit[3]
+            jc.chain = jit[4]
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        rc = self.native.mtgp_eval_pointwise_jit(ctypes.byref(pw), fl.prog.data_ptr(), fl.plen.data_ptr(), fl.n_prog,
+                                                 fl.L, P, ctypes.byref(jc), stream)
+        if rc != nat.OK:
+            raise RuntimeError(f"mtgp_eval_pointwise rejected the configuration (code {rc})")
+        if check:
+            self.check_status(fl)
+        res["_flat"] = fl
+        return res
 
     def eval_programs(self, fl: Flattened, data_vectors: torch.Tensor) -> torch.Tensor:
         """Batched tree_evaluator: every program on M data vectors -> [P, n_prog, M]."""

@@ -534,5 +534,75 @@ class SREvaluator(_CandidateAPI):
         return specs, roles
 
 
-__all__ = ["RK4", "Euler", "Heun", "Midpoint", "Ralston", "Bosh3", "ConstantStepSize", "Dopri5", "PIDController", "DynamicEvaluator", "FeedforwardEvaluator", "SREvaluator",
+class PointwiseEvaluator:
+    """Static symbolic regression y = f(x) on a table of samples: no ODE, no reference plugin of
+    its own -- the fitness a user of the reference writes on top of ``tree_evaluator`` (gp.py:390-433),
+    here one fused HIP kernel (k_pointwise, DESIGN.md "Pointwise evaluator").
+
+    data = (X [M, n_var], Y [M, n_out]); a candidate has n_out trees over the variables x0 ..
+    x{n_var-1} (``layer_sizes = [n_out]``).  Fitness: mean over the points of sum_d (f_d(x_m) -
+    Y[m, d])^2 in the float32 order of include/mtgp.h, a non-finite mean -> max_fitness, clipped to
+    [0, max_fitness].  Evaluation only (no coefficient optimisation)."""
+    model_id = nat.MODEL_POINTWISE
+    state_size = 0
+    dt0 = 0.0
+
+    def __init__(self, max_fitness: float = 1e4):
+        self.max_fitness = float(max_fitness)
+        if not self.max_fitness >= 0:
+            raise ValueError("max_fitness must be >= 0")
+        self._n_var = self._n_out = None
+
+    def prepare(self, data) -> dict:
+        """(X, Y) -> the kernel's transposed rows xt [n_var, ld], yt [n_out, ld]: ld = M rounded up
+        to a multiple of 4 (16-byte row pieces), zero padding."""
+        X, Y = _f32(data[0]), _f32(data[1])
+        if X.ndim != 2 or Y.ndim != 2:
+            raise ValueError("X must be [M, n_var] and Y [M, n_out]")
+        (M, nv), no = X.shape, Y.shape[1]
+        if Y.shape[0] != M:
+            raise ValueError(f"X has {M} points, Y has {Y.shape[0]}")
+        if M < 1:
+            raise ValueError("at least one data point is needed")
+        if not 1 <= nv <= nat.PW_MAX_VAR:
+            raise NotImplementedError(f"n_var {nv}: the pointwise kernel reads 1 .. {nat.PW_MAX_VAR} inputs")
+        if not 1 <= no <= nat.PW_MAX_OUT:
+            raise NotImplementedError(f"n_out {no}: the pointwise kernel runs 1 .. {nat.PW_MAX_OUT} trees")
+        ld = (M + 3) // 4 * 4
+        xt, yt = np.zeros((nv, ld), np.float32), np.zeros((no, ld), np.float32)
+        xt[:, :M], yt[:, :M] = X.T, Y.T
+        self._n_var, self._n_out = nv, no
+        return dict(xt=xt, yt=yt, M=M, ld=ld, n_var=nv, n_out=no)
+
+    def n_trees(self) -> int:
+        return self._n_out
+
+    def n_data(self) -> int:
+        return self._n_var
+
+    def program_specs(self):
+        specs = [(k, self._n_var, 0) for k in range(self._n_out)]
+        roles = dict(prog_state=0, prog_readout=-1, prog_readout_save=-1, readout_save_same=0)
+        return specs, roles
+
+    def _single(self, candidate, data, tree_evaluator, pred: bool):
+        import torch
+        if not hasattr(tree_evaluator, "engine"):
+            raise TypeError("tree_evaluator must be GeneticProgramming.vmap_foriloop of multitreegp_amd")
+        eng = tree_evaluator.engine(self)
+        cand = np.ascontiguousarray(np.asarray(candidate, dtype=np.float32)[None])
+        return eng.evaluate(torch.from_numpy(cand).to(eng.device), data, trajectories=pred)
+
+    def __call__(self, coefficients, nodes, data, tree_evaluator) -> float:
+        """One candidate -> clipped fitness (no parsimony)."""
+        cand = np.concatenate([np.asarray(nodes, np.float32), np.asarray(coefficients, np.float32)], axis=-1)
+        return float(self._single(cand, data, tree_evaluator, False)["fitness"][0].item())
+
+    def evaluate_candidate(self, candidate, data, tree_evaluator):
+        """-> (fitness, pred [M, n_out]), the pair of the SR evaluator (sr.py:47-55)."""
+        res = self._single(candidate, data, tree_evaluator, True)
+        return np.float32(res["fitness"][0].item()), np.ascontiguousarray(res["pred"][0].cpu().numpy().T)
+
+
+__all__ = ["RK4", "Euler", "Heun", "Midpoint", "Ralston", "Bosh3", "ConstantStepSize", "Dopri5", "PIDController", "DynamicEvaluator", "FeedforwardEvaluator", "SREvaluator", "PointwiseEvaluator",
            "fixed_schedule", "rk4_schedule", "constant_step_grid", "adaptive_schedule", "acrobot_mask"]

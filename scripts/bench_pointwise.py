@@ -1,0 +1,103 @@
+"""Pointwise regression: the fused kernel (PointwiseEvaluator -> k_pointwise) against the route it
+replaces (DeviceEngine.eval_programs, then the fitness in torch), in one process, alternating.
+
+P = 8192 candidates of one depth <= 10 tree over two inputs, M = 256, 4096 and 65536 points.  Two
+timings per route and M, host clock around work that ends in a device synchronise, after warm-up:
+  step: what a generation pays -- flatten included (the fused route also schedules and builds its JIT code);
+  eval: the evaluation of an already flattened population (the fused route's code already built).
+Prints one JSON line per M and writes them to --out (default profiles/pointwise/bench.json)."""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import multitreegp_amd as mt  # noqa: E402
+from multitreegp_amd.engine import DeviceEngine  # noqa: E402
+from multitreegp_amd.evaluators import _TreeOnly  # noqa: E402
+from multitreegp_amd.sampling import sample_population  # noqa: E402
+
+MAXF, PARSIMONY = 1e4, 0.01
+
+
+def torch_fitness(pred, y_t, nodes):
+    """The fitness on top of eval_programs' [P, n_out, M] predictions, as a user writes it in torch."""
+    mean = ((pred - y_t[None]) ** 2).sum(1).mean(-1)
+    mean = torch.where(torch.isfinite(mean), mean, torch.full_like(mean, MAXF)).clamp(0.0, MAXF)
+    return mean + PARSIMONY * nodes.float()
+
+
+def timed(fn, reps):
+    out = []
+    for _ in range(reps):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        out.append((time.perf_counter() - t0) * 1e3)
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--P", type=int, default=8192)
+    ap.add_argument("--points", type=int, nargs="+", default=[256, 4096, 65536])
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--out", default=os.path.join("profiles", "pointwise", "bench.json"))
+    a = ap.parse_args()
+    assert torch.cuda.is_available(), "bench_pointwise needs the GPU"
+    ops = [("+", None, 2, 0.5), ("-", None, 2, 0.1), ("*", None, 2, 0.5), ("/", None, 2, 0.1),
+           ("sin", None, 1, 0.1), ("cos", None, 1, 0.1), ("exp", None, 1, 0.1)]
+    lib = mt.NodeLibrary(ops, [["x0", "x1"]], [1])
+    pop = torch.from_numpy(sample_population(0, lib, a.P, 1, max_init_depth=10, max_nodes=63)[0]).cuda()
+    rng = np.random.default_rng(1)
+    lines = []
+    for M in a.points:
+        X = rng.uniform(-2, 2, size=(M, 2)).astype(np.float32)
+        Y = (np.sin(X[:, :1]) * X[:, 1:]).astype(np.float32)
+        new = DeviceEngine(mt.PointwiseEvaluator(MAXF), lib, PARSIMONY, "cuda:0")
+        new_eval = DeviceEngine(mt.PointwiseEvaluator(MAXF), lib, PARSIMONY, "cuda:0")  # (keeps its built code)
+        old = DeviceEngine(_TreeOnly(1, 2), lib, 0.0, "cuda:0")
+        old.prepare_data(None)
+        x_dev, y_t = torch.from_numpy(X).cuda(), torch.from_numpy(Y.T.copy()).cuda()
+        fl_new, fl_old = new_eval.evaluate(pop, (X, Y))["_flat"], old.flatten(pop)
+
+        def torch_step():
+            fl = old.flatten(pop)
+            return torch_fitness(old.eval_programs(fl, x_dev), y_t, fl.nodes)
+
+        routes = {
+            "fused_step": lambda: new.evaluate(pop, (X, Y), check=False)["fitness"],
+            "torch_step": torch_step,
+            "fused_eval": lambda: new_eval.evaluate(pop, (X, Y), flattened=fl_new, check=False)["fitness"],
+            "torch_eval": lambda: torch_fitness(old.eval_programs(fl_old, x_dev), y_t, fl_old.nodes),
+        }
+        f_new, f_old = routes["fused_eval"]().cpu().numpy(), routes["torch_eval"]().cpu().numpy()
+        ms = {k: [] for k in routes}
+        for r in range(a.warmup + a.reps):  # alternating: one call of every route per round
+            for k, fn in routes.items():
+                t = timed(fn, 1)
+                if r >= a.warmup:
+                    ms[k] += t
+        line = dict(bench="pointwise", P=a.P, M=M, n_var=2, n_out=1, reps=a.reps,
+                    max_rel_diff=float(np.max(np.abs(f_new - f_old) / np.maximum(np.abs(f_old), 1e-30))),
+                    **{f"{k}_ms": dict(median=statistics.median(v), min=min(v), max=max(v)) for k, v in ms.items()})
+        for kind in ("step", "eval"):
+            line[f"{kind}_ratio_torch_over_fused"] = line[f"torch_{kind}_ms"]["median"] / line[f"fused_{kind}_ms"]["median"]
+        print(json.dumps(line), flush=True)
+        lines.append(line)
+        del routes, new, new_eval, old, fl_new, fl_old
+        torch.cuda.empty_cache()
+    os.makedirs(os.path.dirname(a.out) or ".", exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(lines, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()
