@@ -480,6 +480,39 @@ int mtgp_eval_pointwise(const MtgpPointwise* pw, const MtgpInstr* prog, const in
 int mtgp_eval_pointwise_jit(const MtgpPointwise* pw, const MtgpInstr* prog, const int32_t* plen, int32_t n_prog,
                             int32_t L, int32_t P, const MtgpJitCode* jit, void* stream);
 
+/* Linear scaling (Keijzer 2003): the fitness is the mean squared error of the best affine
+ * correction a_d + b_d f_d(x) of every output, a and b in closed form from moments that the fused
+ * kernel accumulates in float64 (in f32, Sff - Sf Sf / M cancels).  The order is the spec (DESIGN.md
+ * "Pointwise evaluator", linear scaling), f64 unless noted, f = f_d(x_m) the f32 program value:
+ *   lane l of a wave holds Sf, Sff, Sfy = 0 and for its points span + l, span + l + 64, ... in
+ *   ascending order does Sf = Sf + f, Sff = fma(f, f, Sff), Sfy = fma(f, y, Sfy) (exact products);
+ *   the xor butterfly (lane ^ 1, ^ 2, ... ^ 32) on each of the 3 n_out doubles; the W span triples
+ *   pairwise in span order (zeros up to the next power of two), as the unscaled span sums;
+ *   per output, n = (double)M, Sy / Syy the sums of y / y y over the points (the caller's, exactly
+ *   rounded): invalid iff Sff is not finite (some f was not); cff = Sff - Sf Sf / n,
+ *   cfy = Sfy - Sf Sy / n, cyy = Syy - Sy Sy / n; degenerate (f scored as a constant) iff
+ *   !(cff > 2^-40 Sff): b = 0, a = Sy / n, sse = cyy; else b = cfy / cff, a = (Sy - b Sf) / n,
+ *   sse = cyy - b cfy; sse = max(sse, 0);
+ *   total = sse_0, + sse_d for d = 1 .. in order; any output invalid: max_fitness, else
+ *   (float)(total / n); then the unscaled epilogue in f32 (non-finite -> max_fitness, clip,
+ *   + parsimony * nodes[p]).  scale[p, d] = ((float)a, (float)b), ((float)(Sy / n), 0) when invalid.
+ * pw->partials is not used; pw->pred, when given, receives the raw (unscaled) f. */
+typedef struct {
+  double sy[MTGP_PW_MAX_OUT];  /* host values: sum over the M points of Y[m, d], exactly rounded */
+  double syy[MTGP_PW_MAX_OUT]; /* host values: sum of Y[m, d]^2, exactly rounded                 */
+  double* moments;             /* [P, W, n_out, 3] device scratch, needed when M > MTGP_PW_SPAN  */
+  float* scale;                /* optional device [P, n_out, 2]: (a, b) per output               */
+} MtgpPointwiseScale;
+
+/* As mtgp_eval_pointwise / mtgp_eval_pointwise_jit (the same arguments, the same refusals; sc NULL
+ * or moments missing with M > MTGP_PW_SPAN: MTGP_ERR_ARG), with linear scaling.  Additive symbols:
+ * the ABI version is unchanged. */
+int mtgp_eval_pointwise_scaled(const MtgpPointwise* pw, const MtgpPointwiseScale* sc, const MtgpInstr* prog,
+                               const int32_t* plen, int32_t n_prog, int32_t L, int32_t P, void* stream);
+int mtgp_eval_pointwise_scaled_jit(const MtgpPointwise* pw, const MtgpPointwiseScale* sc, const MtgpInstr* prog,
+                                   const int32_t* plen, int32_t n_prog, int32_t L, int32_t P,
+                                   const MtgpJitCode* jit, void* stream);
+
 /* ------------------------------------------------- coefficient optimisation */
 /* Loss and forward-mode gradient of the SR fitness w.r.t. K parameters per individual (ABI v11),
  * the value_and_grad of GeneticProgramming.epoch (gp.py:435-452, vmap_gradients gp.py:253).

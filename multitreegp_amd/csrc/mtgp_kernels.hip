@@ -3577,15 +3577,54 @@ struct PwArgs {
   const int32_t* jit_info;
   uint64_t jit_cap;
   int32_t chained;          // programs 0 .. n_out-1 are one role chain
+  MtgpPointwiseScale sc;    // linear scaling (k_pointwise<JIT, true> only)
 };
 
-// sum / M, a non-finite mean -> max_fitness, clip, parsimony: the epilogue of both reductions
-__device__ __forceinline__ float pw_finish(const MtgpPointwise& pw, float sum, int p) {
+// a non-finite mean -> max_fitness, clip, parsimony: the f32 epilogue of every reduction
+__device__ __forceinline__ float pw_epilogue(const MtgpPointwise& pw, float mean, int p) {
   const float mx = pw.max_fitness;
-  float mean = sum / (float)pw.M;
   if (!mtgp_isfinite(mean)) mean = mx;
   mean = mean < 0.0f ? 0.0f : (mean > mx ? mx : mean);
   return mean + pw.parsimony * (float)pw.nodes[p];
+}
+
+// sum / M, then the epilogue: the end of both unscaled reductions
+__device__ __forceinline__ float pw_finish(const MtgpPointwise& pw, float sum, int p) {
+  return pw_epilogue(pw, sum / (float)pw.M, p);
+}
+
+// Linear scaling (mtgp.h MtgpPointwiseScale, steps 4-6 of its spec): the closed form of the best
+// a + b f per output from the f64 moments mo[3 d ..] = (Sf, Sff, Sfy) of individual p, the sum of
+// the outputs' residuals, the f32 epilogue; fitness[p] and scale[p].  The end of both scaled
+// reductions (k_pointwise with W = 1, k_pointwise_scaled_mean), so the bits are the same on either.
+constexpr int kPwMoments = 3 * MTGP_PW_MAX_OUT;
+__device__ __forceinline__ void pw_scaled_finish(const MtgpPointwise& pw, const MtgpPointwiseScale& sc, int p,
+                                                 const double (&mo)[kPwMoments]) {
+  const double n = (double)pw.M;
+  double total = 0.0;
+  bool bad = false;
+#pragma unroll
+  for (int j = 0; j < MTGP_PW_MAX_OUT; ++j) {
+    if (j >= pw.n_out) continue;
+    const double Sf = mo[3 * j], Sff = mo[3 * j + 1], Sfy = mo[3 * j + 2], Sy = sc.sy[j], Syy = sc.syy[j];
+    const bool invalid = !(Sff <= 0x1.fffffffffffffp+1023);  // (Sff >= 0 or NaN) some f was non-finite: Sff sums squares that cannot overflow
+    const double cff = Sff - Sf * Sf / n, cfy = Sfy - Sf * Sy / n, cyy = Syy - Sy * Sy / n;
+    double b = 0.0, a = Sy / n, sse = cyy;  // f constant within the sums' rounding (or invalid): the mean of y
+    if (!invalid && cff > 0x1p-40 * Sff) {
+      b = cfy / cff;
+      a = (Sy - b * Sf) / n;
+      sse = cyy - b * cfy;
+    }
+    sse = sse > 0.0 ? sse : 0.0;
+    total = (j == 0) ? sse : total + sse;
+    bad = bad || invalid;
+    if (sc.scale) {
+      float* o = sc.scale + ((size_t)p * pw.n_out + j) * 2;
+      o[0] = (float)a;
+      o[1] = (float)b;
+    }
+  }
+  pw.fitness[p] = bad ? pw_epilogue(pw, pw.max_fitness, p) : pw_epilogue(pw, (float)(total / n), p);
 }
 
 // the n_out programs of individual p on this wave's chunk: data d[] -> f[]
@@ -3624,7 +3663,10 @@ __device__ __forceinline__ void pw_run(const PwArgs& A, int p, int no, bool jok,
   }
 }
 
-template <bool JIT>
+// SCALED (linear scaling): instead of the squared error a lane keeps the f64 moments Sf, Sff, Sfy
+// of every output (3 n_out doubles, <= 24 VGPRs, live across the JIT calls above their clobber
+// set); same staging, same program paths.
+template <bool JIT, bool SCALED = false>
 __global__ void __launch_bounds__(kPwWaves * kWave) k_pointwise(PwArgs A) {
   __shared__ float4 tile[2][kPwRows * kPwTile / 4];
   __shared__ float work[kPwWaves][kLdsWaveWords];  // the interpreter's data and stack columns
@@ -3673,6 +3715,9 @@ __global__ void __launch_bounds__(kPwWaves * kWave) k_pointwise(PwArgs A) {
   float* dcol = &work[wave][lane];
   float* st = &work[wave][kDMax * kWave + lane];
   float acc = 0.0f;
+  double mo[SCALED ? kPwMoments : 1];
+#pragma unroll
+  for (int k = 0; k < (SCALED ? kPwMoments : 1); ++k) mo[k] = 0.0;
   for (int t = 0; t < nt; ++t) {
     const bool more = t + 1 < nt;
     if (more) fetch(t + 1, nx);  // in flight while this tile is evaluated
@@ -3691,15 +3736,27 @@ __global__ void __launch_bounds__(kPwWaves * kWave) k_pointwise(PwArgs A) {
 #pragma unroll
         for (int j = 0; j < MTGP_PW_MAX_OUT; ++j) f[j] = 0.0f;
         pw_run<JIT>(A, p, no, jok, jtab, lane, d, dcol, st, f);
-        float sq = 0.0f;
+        if constexpr (SCALED) {  // f f and f y are exact in f64: only the three additions round
 #pragma unroll
-        for (int j = 0; j < MTGP_PW_MAX_OUT; ++j) {
-          if (j < no) {
-            const float e = f[j] - tl[(nv + j) * kPwTile + off];
-            sq = (j == 0) ? e * e : sq + e * e;
+          for (int j = 0; j < MTGP_PW_MAX_OUT; ++j) {
+            if (j < no && valid) {
+              const double fd = (double)f[j], yd = (double)tl[(nv + j) * kPwTile + off];
+              mo[3 * j] = mo[3 * j] + fd;
+              mo[3 * j + 1] = __builtin_fma(fd, fd, mo[3 * j + 1]);
+              mo[3 * j + 2] = __builtin_fma(fd, yd, mo[3 * j + 2]);
+            }
           }
+        } else {
+          float sq = 0.0f;
+#pragma unroll
+          for (int j = 0; j < MTGP_PW_MAX_OUT; ++j) {
+            if (j < no) {
+              const float e = f[j] - tl[(nv + j) * kPwTile + off];
+              sq = (j == 0) ? e * e : sq + e * e;
+            }
+          }
+          if (valid) acc = (t == 0 && c == 0) ? sq : acc + sq;  // (a lane's first point lies in the span's first chunk)
         }
-        if (valid) acc = (t == 0 && c == 0) ? sq : acc + sq;  // (a lane's first point lies in the span's first chunk)
         if (A.pw.pred && valid) {
 #pragma unroll
           for (int j = 0; j < MTGP_PW_MAX_OUT; ++j)
@@ -3711,6 +3768,23 @@ __global__ void __launch_bounds__(kPwWaves * kWave) k_pointwise(PwArgs A) {
     __syncthreads();
   }
   if (!live) return;
+  if constexpr (SCALED) {
+#pragma unroll
+    for (int k = 0; k < kPwMoments; ++k) {
+      if (k >= 3 * no) continue;
+      for (int w = 1; w < kWave; w <<= 1) mo[k] = mo[k] + __shfl_xor(mo[k], w, kWave);
+    }
+    if (lane != 0) return;
+    if (W > 1) {
+      double* o = A.sc.moments + ((size_t)p * W + sp) * (3 * no);
+#pragma unroll
+      for (int k = 0; k < kPwMoments; ++k)
+        if (k < 3 * no) o[k] = mo[k];
+    } else {
+      pw_scaled_finish(A.pw, A.sc, p, mo);
+    }
+    return;
+  }
   float v = acc;  // (+0 in a lane without a point)
   for (int w = 1; w < kWave; w <<= 1) v = v + __shfl_xor(v, w, kWave);
   if (lane != 0) return;
@@ -3735,6 +3809,43 @@ __global__ void __launch_bounds__(256) k_pointwise_mean(MtgpPointwise pw, int P,
     cst[lvl] = x;
   }
   pw.fitness[p] = pw_finish(pw, cst[top], p);
+}
+
+// The same for linear scaling: each of the 3 n_out moments over the W span triples of
+// moments[P, W, n_out, 3], then pw_scaled_finish.  The counter's levels are unrolled (W <= 2^19
+// spans of an int32 M), so the stack stays in registers; the last span's carry chain ends in the
+// total.
+constexpr int kPwLevels = 20;
+__device__ __forceinline__ double pw_span_tree(const double* src, int stride, int W, int np2) {
+  double cst[kPwLevels], x = 0.0;
+#pragma unroll
+  for (int l = 0; l < kPwLevels; ++l) cst[l] = 0.0;
+#pragma unroll 1
+  for (int c = 0; c < np2; ++c) {
+    x = c < W ? src[(size_t)c * stride] : 0.0;
+    bool carry = true;
+#pragma unroll
+    for (int l = 0; l < kPwLevels; ++l) {
+      const bool set = ((c >> l) & 1) != 0;
+      if (carry && set) x = cst[l] + x;
+      if (carry && !set) cst[l] = x;
+      carry = carry && set;
+    }
+  }
+  return x;
+}
+
+__global__ void __launch_bounds__(256) k_pointwise_scaled_mean(MtgpPointwise pw, MtgpPointwiseScale sc, int P, int W) {
+  const int p = blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= P) return;
+  int np2 = 1;
+  while (np2 < W) np2 <<= 1;
+  const int stride = 3 * pw.n_out;
+  double mo[kPwMoments];
+#pragma unroll
+  for (int k = 0; k < kPwMoments; ++k)
+    mo[k] = k < stride ? pw_span_tree(sc.moments + (size_t)p * W * stride + k, stride, W, np2) : 0.0;
+  pw_scaled_finish(pw, sc, p, mo);
 }
 #endif
 
@@ -5722,15 +5833,19 @@ int mtgp_tu_launch_sr(const void* A_, const MtgpModel* model, const MtgpLaunchCt
 #endif
 
 // the pointwise regression kernels (MTGP_TU 11): one wave per (individual, span), then the span sums
-MTGP_HIDDEN int mtgp_tu_launch_pointwise(const void* A, bool jit, hipStream_t s);
+MTGP_HIDDEN int mtgp_tu_launch_pointwise(const void* A, bool jit, bool scaled, hipStream_t s);
 #if MTGP_TU_POINTWISE
-int mtgp_tu_launch_pointwise(const void* A_, bool jit, hipStream_t s) {
+int mtgp_tu_launch_pointwise(const void* A_, bool jit, bool scaled, hipStream_t s) {
   const PwArgs& A = *(const PwArgs*)A_;
   const dim3 grid((unsigned)(((long)A.P + kPwWaves - 1) / kPwWaves * A.W)), block(kPwWaves * kWave);
+  const dim3 mgrid((unsigned)((A.P + 255) / 256)), mblock(256);
   return launch_checked([&] {
-    mtgp::with_flag(jit, [&](auto J) { hipLaunchKernelGGL((k_pointwise<J()>), grid, block, 0, s, A); });
-    if (A.W > 1)
-      hipLaunchKernelGGL(k_pointwise_mean, dim3((unsigned)((A.P + 255) / 256)), dim3(256), 0, s, A.pw, A.P, A.W);
+    mtgp::with_flag(jit, [&](auto J) {
+      if (scaled) hipLaunchKernelGGL((k_pointwise<J(), true>), grid, block, 0, s, A);
+      else hipLaunchKernelGGL((k_pointwise<J()>), grid, block, 0, s, A);
+    });
+    if (A.W > 1 && scaled) hipLaunchKernelGGL(k_pointwise_scaled_mean, mgrid, mblock, 0, s, A.pw, A.sc, A.P, A.W);
+    else if (A.W > 1) hipLaunchKernelGGL(k_pointwise_mean, mgrid, mblock, 0, s, A.pw, A.P, A.W);
   });
 }
 #endif
@@ -6344,6 +6459,10 @@ int mtgp_eval_rk4_jit(const MtgpModel* model, const MtgpInstr* prog, const int32
   return hipGetLastError() == hipSuccess ? MTGP_OK : MTGP_ERR_LAUNCH;
 }
 
+static int eval_pointwise(const MtgpPointwise* pw, const MtgpPointwiseScale* sc, bool scaled, const MtgpInstr* prog,
+                          const int32_t* plen, int32_t n_prog, int32_t L, int32_t P, const MtgpJitCode* jitc,
+                          void* stream);
+
 int mtgp_eval_pointwise(const MtgpPointwise* pw, const MtgpInstr* prog, const int32_t* plen, int32_t n_prog,
                         int32_t L, int32_t P, void* stream) {
   return mtgp_eval_pointwise_jit(pw, prog, plen, n_prog, L, P, nullptr, stream);
@@ -6351,7 +6470,27 @@ int mtgp_eval_pointwise(const MtgpPointwise* pw, const MtgpInstr* prog, const in
 
 int mtgp_eval_pointwise_jit(const MtgpPointwise* pw, const MtgpInstr* prog, const int32_t* plen, int32_t n_prog,
                             int32_t L, int32_t P, const MtgpJitCode* jitc, void* stream) {
+  return eval_pointwise(pw, nullptr, false, prog, plen, n_prog, L, P, jitc, stream);
+}
+
+int mtgp_eval_pointwise_scaled(const MtgpPointwise* pw, const MtgpPointwiseScale* sc, const MtgpInstr* prog,
+                               const int32_t* plen, int32_t n_prog, int32_t L, int32_t P, void* stream) {
+  return eval_pointwise(pw, sc, true, prog, plen, n_prog, L, P, nullptr, stream);
+}
+
+int mtgp_eval_pointwise_scaled_jit(const MtgpPointwise* pw, const MtgpPointwiseScale* sc, const MtgpInstr* prog,
+                                   const int32_t* plen, int32_t n_prog, int32_t L, int32_t P,
+                                   const MtgpJitCode* jitc, void* stream) {
+  return eval_pointwise(pw, sc, true, prog, plen, n_prog, L, P, jitc, stream);
+}
+
+// every pointwise entry: the refusals (before any device call), PwArgs, the unit's launch.  scaled:
+// linear scaling from sc, whose moments take the place of pw->partials.
+static int eval_pointwise(const MtgpPointwise* pw, const MtgpPointwiseScale* sc, bool scaled, const MtgpInstr* prog,
+                          const int32_t* plen, int32_t n_prog, int32_t L, int32_t P, const MtgpJitCode* jitc,
+                          void* stream) {
   if (!pw || !prog || !plen || !pw->xt || !pw->yt || !pw->nodes || !pw->fitness) return MTGP_ERR_ARG;
+  if (scaled && !sc) return MTGP_ERR_ARG;
   if (P < 0 || L <= 0 || (L & 3) != 0 || n_prog <= 0 || n_prog > MTGP_MAX_PROGRAMS) return MTGP_ERR_ARG;
   if (pw->n_var < 1 || pw->n_var > MTGP_PW_MAX_VAR || pw->n_out < 1 || pw->n_out > MTGP_PW_MAX_OUT ||
       pw->n_out > n_prog)
@@ -6360,7 +6499,7 @@ int mtgp_eval_pointwise_jit(const MtgpPointwise* pw, const MtgpInstr* prog, cons
   if (((reinterpret_cast<uintptr_t>(pw->xt) | reinterpret_cast<uintptr_t>(pw->yt)) & 15u) != 0) return MTGP_ERR_ARG;
   if (!(pw->max_fitness >= 0.0f)) return MTGP_ERR_ARG;
   const int W = (int)(((long)pw->M + MTGP_PW_SPAN - 1) / MTGP_PW_SPAN);
-  if (W > 1 && !pw->partials) return MTGP_ERR_ARG;
+  if (W > 1 && !(scaled ? (const void*)sc->moments : (const void*)pw->partials)) return MTGP_ERR_ARG;
   if (((long)P + kPwWaves - 1) / kPwWaves * W > (long)INT32_MAX) return MTGP_ERR_ARG;
   const bool jit = jitc && jitc->code && jitc->offsets;
   int chained = 0;
@@ -6383,8 +6522,9 @@ int mtgp_eval_pointwise_jit(const MtgpPointwise* pw, const MtgpInstr* prog, cons
   A.jit_info = jit ? jitc->info : nullptr;
   A.jit_cap = jit ? jitc->capacity : 0;
   A.chained = chained;
+  A.sc = scaled ? *sc : MtgpPointwiseScale{};
   hipStream_t s = (hipStream_t)stream;
-  return launch_timed([&] { return mtgp_tu_launch_pointwise(&A, jit, s); }, s);
+  return launch_timed([&] { return mtgp_tu_launch_pointwise(&A, jit, scaled, s); }, s);
 }
 
 }  // extern "C"

@@ -588,7 +588,9 @@ class DeviceEngine:
     def _evaluate_pointwise(self, pop: torch.Tensor, data, predictions: bool, flattened: Optional[Flattened],
                             check: bool, schedule: bool) -> dict:
         """PointwiseEvaluator: flatten, schedule and JIT build as for the ODE evaluators (lane set 64:
-        one individual per unit, the longest programs first), then mtgp_eval_pointwise_jit."""
+        one individual per unit, the longest programs first), then mtgp_eval_pointwise_jit -- or, with
+        the evaluator's linear_scaling, mtgp_eval_pointwise_scaled_jit, which also gives scale
+        [P, n_out, 2] = (a, b) per output (pred stays the raw f)."""
         d = self.prepare_data(data)
         fl = flattened if flattened is not None else self.flatten(pop)
         P, dev = pop.shape[0], self.device
@@ -601,7 +603,16 @@ class DeviceEngine:
         pw.n_var, pw.n_out = d["n_var"], n_out
         pw.max_fitness, pw.parsimony = self.ff.max_fitness, self.parsimony
         pw.nodes, pw.order, pw.fitness = fl.nodes.data_ptr(), _ptr(order), res["fitness"].data_ptr()
-        if W > 1:  # span sums of the individuals whose points take several waves
+        scaled = getattr(self.ff, "linear_scaling", False)
+        sc = nat.MtgpPointwiseScale()
+        if scaled:
+            sc.sy[:n_out], sc.syy[:n_out] = d["sy"].tolist(), d["syy"].tolist()
+            res["scale"] = torch.empty((P, n_out, 2), dtype=torch.float32, device=dev)
+            sc.scale = res["scale"].data_ptr()
+        if W > 1 and scaled:  # span moments / sums of the individuals whose points take several waves
+            res["_moments"] = torch.empty((P, W, n_out, 3), dtype=torch.float64, device=dev)
+            sc.moments = res["_moments"].data_ptr()
+        elif W > 1:
             res["_partials"] = torch.empty((P, W), dtype=torch.float32, device=dev)
             pw.partials = res["_partials"].data_ptr()
         if predictions:
@@ -613,8 +624,11 @@ class DeviceEngine:
             jc.code, jc.offsets, jc.info, jc.capacity = jit[0], jit[1].data_ptr(), jit[2].data_ptr(), jit[3]
             jc.chain = jit[4]
         stream = torch.cuda.current_stream(dev).cuda_stream
-        rc = self.native.mtgp_eval_pointwise_jit(ctypes.byref(pw), fl.prog.data_ptr(), fl.plen.data_ptr(), fl.n_prog,
-                                                 fl.L, P, ctypes.byref(jc), stream)
+        args = (fl.prog.data_ptr(), fl.plen.data_ptr(), fl.n_prog, fl.L, P, ctypes.byref(jc), stream)
+        if scaled:
+            rc = self.native.mtgp_eval_pointwise_scaled_jit(ctypes.byref(pw), ctypes.byref(sc), *args)
+        else:
+            rc = self.native.mtgp_eval_pointwise_jit(ctypes.byref(pw), *args)
         if rc != nat.OK:
             raise RuntimeError(f"mtgp_eval_pointwise rejected the configuration (code {rc})")
         if check:

@@ -18,6 +18,7 @@ evaluators (every environment) and for ``SREvaluator``.
 """
 from __future__ import annotations
 
+import math
 from typing import List, Optional, Tuple
 
 import numpy as np
@@ -542,20 +543,29 @@ class PointwiseEvaluator:
     data = (X [M, n_var], Y [M, n_out]); a candidate has n_out trees over the variables x0 ..
     x{n_var-1} (``layer_sizes = [n_out]``).  Fitness: mean over the points of sum_d (f_d(x_m) -
     Y[m, d])^2 in the float32 order of include/mtgp.h, a non-finite mean -> max_fitness, clipped to
-    [0, max_fitness].  Evaluation only (no coefficient optimisation)."""
+    [0, max_fitness].  Evaluation only (no coefficient optimisation).
+
+    linear_scaling=True (Keijzer 2003): a tree is scored by the error of its best affine correction
+    a_d + b_d f_d(x), slope and intercept in closed form from float64 moments that the same fused
+    kernel accumulates (include/mtgp.h MtgpPointwiseScale); the engine returns them as ``scale``
+    [P, n_out, 2] and ``evaluate_candidate`` applies them.  An output whose relative spread over the
+    points is under about 2^-20 is scored as a constant (b = 0, a = mean y)."""
     model_id = nat.MODEL_POINTWISE
     state_size = 0
     dt0 = 0.0
 
-    def __init__(self, max_fitness: float = 1e4):
+    def __init__(self, max_fitness: float = 1e4, linear_scaling: bool = False):
         self.max_fitness = float(max_fitness)
+        self.linear_scaling = bool(linear_scaling)
         if not self.max_fitness >= 0:
             raise ValueError("max_fitness must be >= 0")
         self._n_var = self._n_out = None
 
     def prepare(self, data) -> dict:
         """(X, Y) -> the kernel's transposed rows xt [n_var, ld], yt [n_out, ld]: ld = M rounded up
-        to a multiple of 4 (16-byte row pieces), zero padding."""
+        to a multiple of 4 (16-byte row pieces), zero padding.  With linear scaling also sy, syy
+        [n_out] float64: the exactly rounded sums of y and y^2 over the points (math.fsum; the squares
+        of float32 values are exact in float64)."""
         X, Y = _f32(data[0]), _f32(data[1])
         if X.ndim != 2 or Y.ndim != 2:
             raise ValueError("X must be [M, n_var] and Y [M, n_out]")
@@ -572,7 +582,12 @@ class PointwiseEvaluator:
         xt, yt = np.zeros((nv, ld), np.float32), np.zeros((no, ld), np.float32)
         xt[:, :M], yt[:, :M] = X.T, Y.T
         self._n_var, self._n_out = nv, no
-        return dict(xt=xt, yt=yt, M=M, ld=ld, n_var=nv, n_out=no)
+        d = dict(xt=xt, yt=yt, M=M, ld=ld, n_var=nv, n_out=no)
+        if self.linear_scaling:
+            y64 = Y.astype(np.float64)
+            d["sy"] = np.array([math.fsum(y64[:, k]) for k in range(no)], np.float64)
+            d["syy"] = np.array([math.fsum(y64[:, k] * y64[:, k]) for k in range(no)], np.float64)
+        return d
 
     def n_trees(self) -> int:
         return self._n_out
@@ -599,9 +614,14 @@ class PointwiseEvaluator:
         return float(self._single(cand, data, tree_evaluator, False)["fitness"][0].item())
 
     def evaluate_candidate(self, candidate, data, tree_evaluator):
-        """-> (fitness, pred [M, n_out]), the pair of the SR evaluator (sr.py:47-55)."""
+        """-> (fitness, pred [M, n_out]), the pair of the SR evaluator (sr.py:47-55); with linear
+        scaling pred is the scaled prediction a + b f (float32, on the host: one candidate)."""
         res = self._single(candidate, data, tree_evaluator, True)
-        return np.float32(res["fitness"][0].item()), np.ascontiguousarray(res["pred"][0].cpu().numpy().T)
+        pred = np.ascontiguousarray(res["pred"][0].cpu().numpy().T)
+        if self.linear_scaling:
+            ab = res["scale"][0].cpu().numpy()
+            pred = ab[:, 0] + ab[:, 1] * pred
+        return np.float32(res["fitness"][0].item()), pred
 
 
 __all__ = ["RK4", "Euler", "Heun", "Midpoint", "Ralston", "Bosh3", "ConstantStepSize", "Dopri5", "PIDController", "DynamicEvaluator", "FeedforwardEvaluator", "SREvaluator", "PointwiseEvaluator",

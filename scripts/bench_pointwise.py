@@ -5,7 +5,12 @@ P = 8192 candidates of one depth <= 10 tree over two inputs, M = 256, 4096 and 6
 timings per route and M, host clock around work that ends in a device synchronise, after warm-up:
   step: what a generation pays -- flatten included (the fused route also schedules and builds its JIT code);
   eval: the evaluation of an already flattened population (the fused route's code already built).
-Prints one JSON line per M and writes them to --out (default profiles/pointwise/bench.json)."""
+Prints one JSON line per M and writes them to --out (default profiles/pointwise/bench.json).
+
+--scaled times linear scaling instead, "eval" only, three routes alternating: the scaled fused kernel
+(k_pointwise<JIT, true>), the unscaled fused kernel of the same build, and the route scaling replaces --
+the fused kernel's predictions [P, n_out, M] reduced by a float64 closed form in torch (default --out
+profiles/pointwise/bench_scaled.json)."""
 import argparse
 import json
 import os
@@ -32,6 +37,17 @@ def torch_fitness(pred, y_t, nodes):
     return mean + PARSIMONY * nodes.float()
 
 
+def torch_scaled_fitness(pred, y_t, nodes):
+    """Linear scaling on top of predictions, as a user writes it in torch: centred float64 moments."""
+    f, y = pred.double(), y_t.double()[None]
+    fc, yc = f - f.mean(-1, keepdim=True), y - y.mean(-1, keepdim=True)
+    cff, cfy, cyy = (fc * fc).sum(-1), (fc * yc).sum(-1), (yc * yc).sum(-1)
+    b = torch.where(cff > 2.0 ** -40 * (f * f).sum(-1), cfy / cff, torch.zeros_like(cff))
+    mean = ((cyy - b * cfy).clamp_min(0.0).sum(1) / pred.shape[-1]).float()
+    mean = torch.where(torch.isfinite(mean), mean, torch.full_like(mean, MAXF)).clamp(0.0, MAXF)
+    return mean + PARSIMONY * nodes.float()
+
+
 def timed(fn, reps):
     out = []
     for _ in range(reps):
@@ -49,8 +65,10 @@ def main():
     ap.add_argument("--points", type=int, nargs="+", default=[256, 4096, 65536])
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--out", default=os.path.join("profiles", "pointwise", "bench.json"))
+    ap.add_argument("--scaled", action="store_true", help="time linear scaling (see the module docstring)")
+    ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    a.out = a.out or os.path.join("profiles", "pointwise", "bench_scaled.json" if a.scaled else "bench.json")
     assert torch.cuda.is_available(), "bench_pointwise needs the GPU"
     ops = [("+", None, 2, 0.5), ("-", None, 2, 0.1), ("*", None, 2, 0.5), ("/", None, 2, 0.1),
            ("sin", None, 1, 0.1), ("cos", None, 1, 0.1), ("exp", None, 1, 0.1)]
@@ -78,7 +96,18 @@ def main():
             "fused_eval": lambda: new_eval.evaluate(pop, (X, Y), flattened=fl_new, check=False)["fitness"],
             "torch_eval": lambda: torch_fitness(old.eval_programs(fl_old, x_dev), y_t, fl_old.nodes),
         }
-        f_new, f_old = routes["fused_eval"]().cpu().numpy(), routes["torch_eval"]().cpu().numpy()
+        if a.scaled:
+            sc = DeviceEngine(mt.PointwiseEvaluator(MAXF, linear_scaling=True), lib, PARSIMONY, "cuda:0")
+            fl_sc = sc.evaluate(pop, (X, Y))["_flat"]
+
+            def torch_scaled():
+                res = new_eval.evaluate(pop, (X, Y), trajectories=True, flattened=fl_new, check=False)
+                return torch_scaled_fitness(res["pred"], y_t, fl_new.nodes)
+
+            routes = {"scaled_eval": lambda: sc.evaluate(pop, (X, Y), flattened=fl_sc, check=False)["fitness"],
+                      "fused_eval": routes["fused_eval"], "torch_eval": torch_scaled}
+        first = "scaled_eval" if a.scaled else "fused_eval"
+        f_new, f_old = routes[first]().cpu().numpy(), routes["torch_eval"]().cpu().numpy()
         ms = {k: [] for k in routes}
         for r in range(a.warmup + a.reps):  # alternating: one call of every route per round
             for k, fn in routes.items():
@@ -88,11 +117,17 @@ def main():
         line = dict(bench="pointwise", P=a.P, M=M, n_var=2, n_out=1, reps=a.reps,
                     max_rel_diff=float(np.max(np.abs(f_new - f_old) / np.maximum(np.abs(f_old), 1e-30))),
                     **{f"{k}_ms": dict(median=statistics.median(v), min=min(v), max=max(v)) for k, v in ms.items()})
-        for kind in ("step", "eval"):
+        if a.scaled:
+            med = {k: line[f"{k}_ms"]["median"] for k in routes}
+            line["bench"] = "pointwise_scaled"
+            line["ratio_scaled_over_unscaled"] = med["scaled_eval"] / med["fused_eval"]
+            line["ratio_torch_over_scaled"] = med["torch_eval"] / med["scaled_eval"]
+        for kind in () if a.scaled else ("step", "eval"):
             line[f"{kind}_ratio_torch_over_fused"] = line[f"torch_{kind}_ms"]["median"] / line[f"fused_{kind}_ms"]["median"]
         print(json.dumps(line), flush=True)
         lines.append(line)
         del routes, new, new_eval, old, fl_new, fl_old
+        sc = fl_sc = None
         torch.cuda.empty_cache()
     os.makedirs(os.path.dirname(a.out) or ".", exist_ok=True)
     with open(a.out, "w") as f:
