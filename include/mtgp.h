@@ -453,13 +453,18 @@ int mtgp_eval_rk4_jit(const MtgpModel* model, const MtgpInstr* prog, const int32
 #define MTGP_PW_SPAN 4096
 #define MTGP_PW_MAX_VAR 8 /* the register-data JIT's data vector v0-v7 */
 #define MTGP_PW_MAX_OUT 4 /* one role chain (v26..v29) */
+/* Tables of MTGP_PW_MAX_VAR + 1 .. MTGP_PW_WIDE_MAX_VAR columns run in the wide kernel, which leaves
+ * the data vector in LDS (every MTGP_MAX_DATA slot of the LDS-data JIT); so does every table when
+ * the environment has MTGP_PW_WIDE=1 (an A/B knob).  The order above does not involve n_var: the
+ * bits do not depend on which kernel ran. */
+#define MTGP_PW_WIDE_MAX_VAR 64
 typedef struct {
   const float* xt;      /* [n_var][ld] inputs, transposed (a chunk load is coalesced); 16-byte aligned */
   const float* yt;      /* [n_out][ld] targets, transposed; 16-byte aligned                           */
   int32_t M;            /* points, >= 1                                                                */
   int32_t ld;           /* row stride of xt / yt in floats: a multiple of 4, >= M (padding is read,    */
                         /* never used)                                                                 */
-  int32_t n_var;        /* 1 .. MTGP_PW_MAX_VAR                                                        */
+  int32_t n_var;        /* 1 .. MTGP_PW_WIDE_MAX_VAR                                                   */
   int32_t n_out;        /* 1 .. MTGP_PW_MAX_OUT                                                        */
   float max_fitness;
   float parsimony;
@@ -476,7 +481,10 @@ int mtgp_eval_pointwise(const MtgpPointwise* pw, const MtgpInstr* prog, const in
 /* With JIT code built in MTGP_JIT_MODE_REGS for lane set 64 and pw->order, its chain either none
  * or programs 0 .. n_out-1 as one role chain (next = bits 0 .. n_out-2); jit NULL or without code:
  * the interpreter.  The kernel interprets too when `info` says the code is unusable.  Identical
- * bits on every path. */
+ * bits on every path.
+ * Where the wide kernel runs (n_var > MTGP_PW_MAX_VAR, or MTGP_PW_WIDE=1) the code must be built in
+ * MTGP_JIT_MODE_LDS instead and without a chain: `next` != 0 is MTGP_ERR_ARG before any device
+ * call.  n_var > MTGP_PW_WIDE_MAX_VAR: MTGP_ERR_ARG. */
 int mtgp_eval_pointwise_jit(const MtgpPointwise* pw, const MtgpInstr* prog, const int32_t* plen, int32_t n_prog,
                             int32_t L, int32_t P, const MtgpJitCode* jit, void* stream);
 

@@ -3577,7 +3577,8 @@ struct PwArgs {
   const int32_t* jit_info;
   uint64_t jit_cap;
   int32_t chained;          // programs 0 .. n_out-1 are one role chain
-  MtgpPointwiseScale sc;    // linear scaling (k_pointwise<JIT, true> only)
+  int32_t chunks;           // 0: k_pointwise; else k_pointwise_wide with this many chunks per tile (pw_wide_chunks)
+  MtgpPointwiseScale sc;    // linear scaling (<JIT, true> only)
 };
 
 // a non-finite mean -> max_fitness, clip, parsimony: the f32 epilogue of every reduction
@@ -3663,6 +3664,73 @@ __device__ __forceinline__ void pw_run(const PwArgs& A, int p, int no, bool jok,
   }
 }
 
+// One chunk's outputs f[] of a lane into its sums (steps 1-2 of the spec; scaled: step 1), and the
+// prediction store.  m: the lane's point; first: its first point (the span's first chunk); the
+// target of output j is ycol[j * ys].  Shared by k_pointwise and k_pointwise_wide: the same bits.
+template <bool SCALED>
+__device__ __forceinline__ void pw_accumulate(const PwArgs& A, int p, int no, int m, bool first,
+                                              const float (&f)[MTGP_PW_MAX_OUT], const float* ycol, int ys,
+                                              float& acc, double (&mo)[SCALED ? kPwMoments : 1]) {
+  const int M = A.pw.M;
+  const bool valid = m < M;
+  if constexpr (SCALED) {  // f f and f y are exact in f64: only the three additions round
+#pragma unroll
+    for (int j = 0; j < MTGP_PW_MAX_OUT; ++j) {
+      if (j < no && valid) {
+        const double fd = (double)f[j], yd = (double)ycol[j * ys];
+        mo[3 * j] = mo[3 * j] + fd;
+        mo[3 * j + 1] = __builtin_fma(fd, fd, mo[3 * j + 1]);
+        mo[3 * j + 2] = __builtin_fma(fd, yd, mo[3 * j + 2]);
+      }
+    }
+  } else {
+    float sq = 0.0f;
+#pragma unroll
+    for (int j = 0; j < MTGP_PW_MAX_OUT; ++j) {
+      if (j < no) {
+        const float e = f[j] - ycol[j * ys];
+        sq = (j == 0) ? e * e : sq + e * e;
+      }
+    }
+    if (valid) acc = first ? sq : acc + sq;  // (a lane's first point lies in the span's first chunk)
+  }
+  if (A.pw.pred && valid) {
+#pragma unroll
+    for (int j = 0; j < MTGP_PW_MAX_OUT; ++j)
+      if (j < no) A.pw.pred[((size_t)p * no + j) * M + m] = f[j];
+  }
+}
+
+// The end of a live wave: the xor butterfly over the lane sums, then lane 0 writes span sp's sum /
+// moments (W > 1: k_pointwise_mean / k_pointwise_scaled_mean finish) or finishes individual p.
+template <bool SCALED>
+__device__ __forceinline__ void pw_reduce(const PwArgs& A, int p, int sp, int no, int lane, float acc,
+                                          double (&mo)[SCALED ? kPwMoments : 1]) {
+  const int W = A.W;
+  if constexpr (SCALED) {
+#pragma unroll
+    for (int k = 0; k < kPwMoments; ++k) {
+      if (k >= 3 * no) continue;
+      for (int w = 1; w < kWave; w <<= 1) mo[k] = mo[k] + __shfl_xor(mo[k], w, kWave);
+    }
+    if (lane != 0) return;
+    if (W > 1) {
+      double* o = A.sc.moments + ((size_t)p * W + sp) * (3 * no);
+#pragma unroll
+      for (int k = 0; k < kPwMoments; ++k)
+        if (k < 3 * no) o[k] = mo[k];
+    } else {
+      pw_scaled_finish(A.pw, A.sc, p, mo);
+    }
+  } else {
+    float v = acc;  // (+0 in a lane without a point)
+    for (int w = 1; w < kWave; w <<= 1) v = v + __shfl_xor(v, w, kWave);
+    if (lane != 0) return;
+    if (W > 1) A.pw.partials[(size_t)p * W + sp] = v;
+    else A.pw.fitness[p] = pw_finish(A.pw, v, p);
+  }
+}
+
 // SCALED (linear scaling): instead of the squared error a lane keeps the f64 moments Sf, Sff, Sfy
 // of every output (3 n_out doubles, <= 24 VGPRs, live across the JIT calls above their clobber
 // set); same staging, same program paths.
@@ -3729,67 +3797,152 @@ __global__ void __launch_bounds__(kPwWaves * kWave) k_pointwise(PwArgs A) {
       for (int c = 0; c < nc; ++c) {
         const int off = c * kWave + lane;
         const int m = m0 + t * kPwTile + off;
-        const bool valid = m < M;
         float d[kDMax], f[MTGP_PW_MAX_OUT];
 #pragma unroll
         for (int k = 0; k < kDMax; ++k) d[k] = k < nv ? tl[k * kPwTile + off] : 0.0f;
 #pragma unroll
         for (int j = 0; j < MTGP_PW_MAX_OUT; ++j) f[j] = 0.0f;
         pw_run<JIT>(A, p, no, jok, jtab, lane, d, dcol, st, f);
-        if constexpr (SCALED) {  // f f and f y are exact in f64: only the three additions round
-#pragma unroll
-          for (int j = 0; j < MTGP_PW_MAX_OUT; ++j) {
-            if (j < no && valid) {
-              const double fd = (double)f[j], yd = (double)tl[(nv + j) * kPwTile + off];
-              mo[3 * j] = mo[3 * j] + fd;
-              mo[3 * j + 1] = __builtin_fma(fd, fd, mo[3 * j + 1]);
-              mo[3 * j + 2] = __builtin_fma(fd, yd, mo[3 * j + 2]);
-            }
-          }
-        } else {
-          float sq = 0.0f;
-#pragma unroll
-          for (int j = 0; j < MTGP_PW_MAX_OUT; ++j) {
-            if (j < no) {
-              const float e = f[j] - tl[(nv + j) * kPwTile + off];
-              sq = (j == 0) ? e * e : sq + e * e;
-            }
-          }
-          if (valid) acc = (t == 0 && c == 0) ? sq : acc + sq;  // (a lane's first point lies in the span's first chunk)
-        }
-        if (A.pw.pred && valid) {
-#pragma unroll
-          for (int j = 0; j < MTGP_PW_MAX_OUT; ++j)
-            if (j < no) A.pw.pred[((size_t)p * no + j) * M + m] = f[j];
-        }
+        pw_accumulate<SCALED>(A, p, no, m, t == 0 && c == 0, f, tl + nv * kPwTile + off, kPwTile, acc, mo);
       }
     }
     if (more) stash((t + 1) & 1, nx);
     __syncthreads();
   }
-  if (!live) return;
-  if constexpr (SCALED) {
+  if (live) pw_reduce<SCALED>(A, p, sp, no, lane, acc, mo);
+}
+
+// Tables of MTGP_PW_MAX_VAR + 1 .. MTGP_PW_WIDE_MAX_VAR columns (MTGP_PW_WIDE=1: any): the same work
+// split, arithmetic and reductions as k_pointwise, with the data vector left in LDS for LDS-data JIT
+// code (mtgp_jit.h kJitModeLds) instead of v0-v7.  A tile is T chunks of 64 points laid out
+// [chunk][row][64 lanes], rows = n_var + n_out (X rows, then Y rows): inside a chunk row k is one
+// 256-byte column, so with v0 = the address of tile[c][0][lane] data slot k sits at + k *
+// MTGP_SLOT_BYTES -- what the code and the interpreter (dcol[k * kWave]) both read, straight from
+// the tile; only the stack columns are per-wave LDS.  Dynamic LDS: two tiles, then kPwWaves stacks.
+// Staging as in k_pointwise; a thread's piece v is (row, chunk, 16-byte piece) in that order, so a
+// row's T * 256 bytes are fetched by T * 16 neighbouring threads.
+// T (PwArgs.chunks) is the largest of 4, 2, 1 that keeps the workgroup within 64 KB, two per CU:
+// rows <= 24: 4, <= 48: 2, <= 68: 1.
+constexpr int kPwWideLds = 64 * 1024;
+constexpr int kPwWideStack = kPwWaves * kSMax * kWave * (int)sizeof(float);
+constexpr int pw_wide_chunks(int rows) {
+  for (int T = 4; T > 1; T >>= 1)
+    if (2 * T * rows * (int)MTGP_SLOT_BYTES + kPwWideStack <= kPwWideLds) return T;
+  return 1;
+}
+constexpr int pw_wide_lds(int rows, int T) { return 2 * T * rows * (int)MTGP_SLOT_BYTES + kPwWideStack; }
+constexpr int kPwWideRows = MTGP_PW_WIDE_MAX_VAR + MTGP_PW_MAX_OUT;
+// float4 per thread and tile: T * rows <= 96 for every rows <= kPwWideRows
+constexpr int kPwWideVecs = (96 * (kWave / 4) + kPwWaves * kWave - 1) / (kPwWaves * kWave);
+static_assert(pw_wide_lds(kPwWideRows, pw_wide_chunks(kPwWideRows)) <= kPwWideLds, "the widest table fits");
+static_assert(4 * 24 <= 96 && 2 * 48 <= 96 && kPwWideRows <= 96, "kPwWideVecs covers every tile");
+
+// the n_out programs of individual p on the chunk whose slot-0 column is col: one LDS-data unit
+// each (that code has no `next` chains: v26.. are its preloads), or the interpreter on the column
+template <bool JIT>
+__device__ __forceinline__ void pw_run_lds(const PwArgs& A, int p, int no, bool jok, uint32_t jtab, int lane,
+                                           const float* col, float* st, float (&f)[MTGP_PW_MAX_OUT]) {
+  uint64_t fl = 0;
+  const bool coded = JIT && jok;
+  if (coded) {
+    const uint32_t la = lds_address(col);
+#pragma unroll 1
+    for (int q = 0; q < no; ++q) {
+      const uint32_t off = (uint32_t)__builtin_amdgcn_readlane((int)jtab, q);
+      const float v = jit_call_lds(A.jit_base + off, la, fl);
 #pragma unroll
-    for (int k = 0; k < kPwMoments; ++k) {
-      if (k >= 3 * no) continue;
-      for (int w = 1; w < kWave; w <<= 1) mo[k] = mo[k] + __shfl_xor(mo[k], w, kWave);
+      for (int j = 0; j < MTGP_PW_MAX_OUT; ++j) f[j] = (q == j) ? v : f[j];
     }
-    if (lane != 0) return;
-    if (W > 1) {
-      double* o = A.sc.moments + ((size_t)p * W + sp) * (3 * no);
-#pragma unroll
-      for (int k = 0; k < kPwMoments; ++k)
-        if (k < 3 * no) o[k] = mo[k];
-    } else {
-      pw_scaled_finish(A.pw, A.sc, p, mo);
-    }
-    return;
+    if (__builtin_expect(fl == 0, 1)) return;
   }
-  float v = acc;  // (+0 in a lane without a point)
-  for (int w = 1; w < kWave; w <<= 1) v = v + __shfl_xor(v, w, kWave);
-  if (lane != 0) return;
-  if (W > 1) A.pw.partials[(size_t)p * W + sp] = v;
-  else A.pw.fitness[p] = pw_finish(A.pw, v, p);
+  const bool mine = !coded || ((fl >> lane) & 1ull) != 0;
+#pragma unroll 1
+  for (int q = 0; q < no; ++q) {
+    const float v = run_prog(A.prog + ((size_t)p * A.n_prog + q) * A.L, col, st);
+#pragma unroll
+    for (int j = 0; j < MTGP_PW_MAX_OUT; ++j) f[j] = (q == j && mine) ? v : f[j];
+  }
+}
+
+// (LDS-data units clobber v8-v59, so what lives across the calls -- the staged pieces, the sums,
+// the inlined interpreter's hoisted constants -- sits above them: <JIT, SCALED> needs 154 VGPRs, one
+// workgroup per CU; bounding it to 128 spills, so it is left unbounded.  The other three fit two.)
+template <bool JIT, bool SCALED = false>
+__global__ void __launch_bounds__(kPwWaves * kWave) k_pointwise_wide(PwArgs A) {
+  extern __shared__ float4 wtile[];  // [2][T][rows][16] | stacks [kPwWaves][kSMax][kWave] floats
+  const int wave = uni(threadIdx.x >> 6), lane = threadIdx.x & 63;
+  const int W = A.W;
+  const int ig = (int)blockIdx.x / W, sp = (int)blockIdx.x - ig * W;
+  const int q = ig * kPwWaves + wave;
+  const bool live = q < A.P;  // (a wave without an individual still stages its share of the tiles)
+  const int p = live ? uni(A.pw.order ? A.pw.order[q] : q) : 0;
+  const int M = A.pw.M, ld = A.pw.ld, nv = A.pw.n_var, no = A.pw.n_out;
+  const int rows = nv + no, T = A.chunks, lt = (T >> 1) + 4;  // T in {1, 2, 4}: lt = log2(16 T)
+  const int tpts = T * kWave;                                 // points of a tile
+  const int m0 = sp * MTGP_PW_SPAN;
+  const int span = M - m0 < MTGP_PW_SPAN ? M - m0 : MTGP_PW_SPAN;
+  const int nt = (span + tpts - 1) / tpts;
+  const int nvec = rows << lt;  // 16-byte pieces of a tile: row v >> lt, points 4 (v & (16 T - 1)) ..
+  bool jok = false;
+  uint32_t jtab = 0;
+  if (JIT) {
+    asm volatile("s_icache_inv");  // the JIT code was written by an earlier kernel
+    jok = true;
+    if (A.jit_info) jok = uni((int)(A.jit_info[0] == 0 && (uint64_t)(uint32_t)A.jit_info[1] <= A.jit_cap)) != 0;
+    if (live && lane < no) jtab = A.jit_off[(size_t)q * A.n_prog + lane];
+  }
+  auto fetch = [&](int t, float4 (&r)[kPwWideVecs]) {
+#pragma unroll
+    for (int k = 0; k < kPwWideVecs; ++k) {
+      const int v = (int)threadIdx.x + k * kPwWaves * kWave;
+      r[k] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+      if (v >= nvec) continue;
+      const int row = v >> lt, pm = m0 + t * tpts + (v & ((1 << lt) - 1)) * 4;
+      if (pm >= ld) continue;  // (ld is a multiple of 4: the piece lies inside the row or past it)
+      const float* src = row < nv ? A.pw.xt + (size_t)row * ld : A.pw.yt + (size_t)(row - nv) * ld;
+      r[k] = *reinterpret_cast<const float4*>(src + pm);
+    }
+  };
+  auto stash = [&](int b, const float4 (&r)[kPwWideVecs]) {
+#pragma unroll
+    for (int k = 0; k < kPwWideVecs; ++k) {
+      const int v = (int)threadIdx.x + k * kPwWaves * kWave;
+      if (v >= nvec) continue;
+      const int row = v >> lt, rem = v & ((1 << lt) - 1);  // rem = 16 chunk + piece
+      wtile[b * nvec + (((rem >> 4) * rows + row) << 4) + (rem & 15)] = r[k];
+    }
+  };
+  float4 nx[kPwWideVecs];
+  fetch(0, nx);
+  stash(0, nx);
+  __syncthreads();
+  float* st = reinterpret_cast<float*>(wtile + 2 * nvec) + wave * (kSMax * kWave) + lane;
+  float acc = 0.0f;
+  double mo[SCALED ? kPwMoments : 1];
+#pragma unroll
+  for (int k = 0; k < (SCALED ? kPwMoments : 1); ++k) mo[k] = 0.0;
+  for (int t = 0; t < nt; ++t) {
+    const bool more = t + 1 < nt;
+    if (more) fetch(t + 1, nx);  // in flight while this tile is evaluated
+    if (live) {
+      const float* tl = reinterpret_cast<const float*>(wtile + (t & 1) * nvec) + lane;
+      const int left = span - t * tpts;
+      const int nc = left >= tpts ? T : (left + kWave - 1) / kWave;
+#pragma unroll 1
+      for (int c = 0; c < nc; ++c) {
+        const float* col = tl + c * rows * kWave;
+        const int m = m0 + t * tpts + c * kWave + lane;
+        float f[MTGP_PW_MAX_OUT];
+#pragma unroll
+        for (int j = 0; j < MTGP_PW_MAX_OUT; ++j) f[j] = 0.0f;
+        pw_run_lds<JIT>(A, p, no, jok, jtab, lane, col, st, f);
+        pw_accumulate<SCALED>(A, p, no, m, t == 0 && c == 0, f, col + nv * kWave, kWave, acc, mo);
+      }
+    }
+    if (more) stash((t + 1) & 1, nx);
+    __syncthreads();
+  }
+  if (live) pw_reduce<SCALED>(A, p, sp, no, lane, acc, mo);
 }
 
 #if MTGP_TU_POINTWISE
@@ -5840,8 +5993,11 @@ int mtgp_tu_launch_pointwise(const void* A_, bool jit, bool scaled, hipStream_t 
   const dim3 grid((unsigned)(((long)A.P + kPwWaves - 1) / kPwWaves * A.W)), block(kPwWaves * kWave);
   const dim3 mgrid((unsigned)((A.P + 255) / 256)), mblock(256);
   return launch_checked([&] {
+    const size_t lds = A.chunks ? (size_t)pw_wide_lds(A.pw.n_var + A.pw.n_out, A.chunks) : 0;
     mtgp::with_flag(jit, [&](auto J) {
-      if (scaled) hipLaunchKernelGGL((k_pointwise<J(), true>), grid, block, 0, s, A);
+      if (A.chunks && scaled) hipLaunchKernelGGL((k_pointwise_wide<J(), true>), grid, block, lds, s, A);
+      else if (A.chunks) hipLaunchKernelGGL((k_pointwise_wide<J()>), grid, block, lds, s, A);
+      else if (scaled) hipLaunchKernelGGL((k_pointwise<J(), true>), grid, block, 0, s, A);
       else hipLaunchKernelGGL((k_pointwise<J()>), grid, block, 0, s, A);
     });
     if (A.W > 1 && scaled) hipLaunchKernelGGL(k_pointwise_scaled_mean, mgrid, mblock, 0, s, A.pw, A.sc, A.P, A.W);
@@ -6492,9 +6648,12 @@ static int eval_pointwise(const MtgpPointwise* pw, const MtgpPointwiseScale* sc,
   if (!pw || !prog || !plen || !pw->xt || !pw->yt || !pw->nodes || !pw->fitness) return MTGP_ERR_ARG;
   if (scaled && !sc) return MTGP_ERR_ARG;
   if (P < 0 || L <= 0 || (L & 3) != 0 || n_prog <= 0 || n_prog > MTGP_MAX_PROGRAMS) return MTGP_ERR_ARG;
-  if (pw->n_var < 1 || pw->n_var > MTGP_PW_MAX_VAR || pw->n_out < 1 || pw->n_out > MTGP_PW_MAX_OUT ||
+  if (pw->n_var < 1 || pw->n_var > MTGP_PW_WIDE_MAX_VAR || pw->n_out < 1 || pw->n_out > MTGP_PW_MAX_OUT ||
       pw->n_out > n_prog)
     return MTGP_ERR_ARG;
+  // k_pointwise_wide: the tables k_pointwise cannot hold in v0-v7, or every table (MTGP_PW_WIDE=1, the A/B knob)
+  const char* force = getenv("MTGP_PW_WIDE");
+  const bool wide = pw->n_var > MTGP_PW_MAX_VAR || (force && strcmp(force, "1") == 0);
   if (pw->M < 1 || pw->ld < pw->M || (pw->ld & 3) != 0) return MTGP_ERR_ARG;
   if (((reinterpret_cast<uintptr_t>(pw->xt) | reinterpret_cast<uintptr_t>(pw->yt)) & 15u) != 0) return MTGP_ERR_ARG;
   if (!(pw->max_fitness >= 0.0f)) return MTGP_ERR_ARG;
@@ -6507,6 +6666,7 @@ static int eval_pointwise(const MtgpPointwise* pw, const MtgpPointwiseScale* sc,
     const MtgpJitChain& ch = jitc->chain;
     const uint32_t want = pw->n_out >= 2 ? (1u << (pw->n_out - 1)) - 1u : 0u;
     if (ch.cond != 0u || ch.store != 0u || ch.put != 0u || (ch.next != 0u && ch.next != want)) return MTGP_ERR_ARG;
+    if (wide && ch.next != 0u) return MTGP_ERR_ARG;  // (LDS-data code has no `next` chains)
     chained = ch.next != 0u;
   }
   if (P == 0) return MTGP_OK;
@@ -6522,6 +6682,7 @@ static int eval_pointwise(const MtgpPointwise* pw, const MtgpPointwiseScale* sc,
   A.jit_info = jit ? jitc->info : nullptr;
   A.jit_cap = jit ? jitc->capacity : 0;
   A.chained = chained;
+  A.chunks = wide ? pw_wide_chunks(pw->n_var + pw->n_out) : 0;
   A.sc = scaled ? *sc : MtgpPointwiseScale{};
   hipStream_t s = (hipStream_t)stream;
   return launch_timed([&] { return mtgp_tu_launch_pointwise(&A, jit, scaled, s); }, s);

@@ -211,7 +211,8 @@ class DeviceEngine:
         if os.environ.get("MTGP_JIT_CHAIN", "1") == "0":
             return ch
         if self.ff.model_id == nat.MODEL_POINTWISE:  # the n_out trees as one chain (mtgp_eval_pointwise_jit)
-            ch.next = (1 << (n_prog - 1)) - 1
+            if not self._pointwise_wide():  # (k_pointwise_wide calls one LDS-data unit per tree)
+                ch.next = (1 << (n_prog - 1)) - 1
             return ch
         if self._jit_mode() == nat.JIT_MODE_LDS and self.ff.model_id != nat.MODEL_SR:
             return ch  # (the runtime-state-size control kernels call one unit per program)
@@ -337,9 +338,19 @@ class DeviceEngine:
             return self.ff.solver_kind != "dopri5"
         return self.ff.n_data() <= 8 or self._jit_mode() == nat.JIT_MODE_LDS
 
+    def _pointwise_wide(self) -> bool:
+        """Whether mtgp_eval_pointwise* will launch k_pointwise_wide: more than PW_MAX_VAR columns, or
+        MTGP_PW_WIDE=1 (the A/B knob, which the C entry reads from the same environment)."""
+        if self.ff.model_id != nat.MODEL_POINTWISE:
+            return False
+        return self.ff.n_data() > nat.PW_MAX_VAR or os.environ.get("MTGP_PW_WIDE", "0") == "1"
+
     def _jit_mode(self) -> int:
-        """LDS-data code for the wide-state SR kernel (n_var > 4), register-data code otherwise."""
+        """LDS-data code for the wide-state SR kernel (n_var > 4) and the wide pointwise kernel,
+        register-data code otherwise."""
         if self.ff.model_id == nat.MODEL_SR and self.ff.n_data() > 4:
+            return nat.JIT_MODE_LDS
+        if self._pointwise_wide():
             return nat.JIT_MODE_LDS
         if getattr(self.ff, "state_size", 0) > 3:  # the runtime-state-size kernels' LDS data vector (round 6)
             return nat.JIT_MODE_LDS

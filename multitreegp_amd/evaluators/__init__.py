@@ -549,14 +549,18 @@ class PointwiseEvaluator:
     a_d + b_d f_d(x), slope and intercept in closed form from float64 moments that the same fused
     kernel accumulates (include/mtgp.h MtgpPointwiseScale); the engine returns them as ``scale``
     [P, n_out, 2] and ``evaluate_candidate`` applies them.  An output whose relative spread over the
-    points is under about 2^-20 is scored as a constant (b = 0, a = mean y)."""
+    points is under about 2^-20 is scored as a constant (b = 0, a = mean y).
+
+    wide=True accepts tables of up to 64 columns: those of more than 8 run in k_pointwise_wide (the
+    data vector in LDS, the same bits); it is opt-in so that the default keeps refusing 9 columns."""
     model_id = nat.MODEL_POINTWISE
     state_size = 0
     dt0 = 0.0
 
-    def __init__(self, max_fitness: float = 1e4, linear_scaling: bool = False):
+    def __init__(self, max_fitness: float = 1e4, linear_scaling: bool = False, wide: bool = False):
         self.max_fitness = float(max_fitness)
         self.linear_scaling = bool(linear_scaling)
+        self.wide = bool(wide)
         if not self.max_fitness >= 0:
             raise ValueError("max_fitness must be >= 0")
         self._n_var = self._n_out = None
@@ -574,8 +578,10 @@ class PointwiseEvaluator:
             raise ValueError(f"X has {M} points, Y has {Y.shape[0]}")
         if M < 1:
             raise ValueError("at least one data point is needed")
-        if not 1 <= nv <= nat.PW_MAX_VAR:
-            raise NotImplementedError(f"n_var {nv}: the pointwise kernel reads 1 .. {nat.PW_MAX_VAR} inputs")
+        max_var = nat.PW_WIDE_MAX_VAR if self.wide else nat.PW_MAX_VAR
+        if not 1 <= nv <= max_var:
+            raise NotImplementedError(f"n_var {nv}: the pointwise kernel reads 1 .. {max_var} inputs"
+                                      + ("" if self.wide else f" ({nat.PW_WIDE_MAX_VAR} with wide=True)"))
         if not 1 <= no <= nat.PW_MAX_OUT:
             raise NotImplementedError(f"n_out {no}: the pointwise kernel runs 1 .. {nat.PW_MAX_OUT} trees")
         ld = (M + 3) // 4 * 4

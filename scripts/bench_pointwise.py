@@ -10,7 +10,12 @@ Prints one JSON line per M and writes them to --out (default profiles/pointwise/
 --scaled times linear scaling instead, "eval" only, three routes alternating: the scaled fused kernel
 (k_pointwise<JIT, true>), the unscaled fused kernel of the same build, and the route scaling replaces --
 the fused kernel's predictions [P, n_out, M] reduced by a float64 closed form in torch (default --out
-profiles/pointwise/bench_scaled.json)."""
+profiles/pointwise/bench_scaled.json).
+
+--n-var N: a table of N columns (default 2; more than 8 run in k_pointwise_wide, the data vector in LDS).
+--wide-ab (N <= 8): "eval" only, two routes alternating -- the same population through k_pointwise_wide
+(MTGP_PW_WIDE=1, LDS-data code) and through k_pointwise (register-data code) of the same build.
+--append adds the lines to --out instead of replacing it (profiles/pointwise/bench_wide.json holds both)."""
 import argparse
 import json
 import os
@@ -66,22 +71,29 @@ def main():
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--scaled", action="store_true", help="time linear scaling (see the module docstring)")
+    ap.add_argument("--n-var", type=int, default=2)
+    ap.add_argument("--wide-ab", action="store_true", help="k_pointwise_wide against k_pointwise (see the module docstring)")
+    ap.add_argument("--append", action="store_true")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
-    a.out = a.out or os.path.join("profiles", "pointwise", "bench_scaled.json" if a.scaled else "bench.json")
+    a.out = a.out or os.path.join("profiles", "pointwise", "bench_scaled.json" if a.scaled else
+                                  "bench_wide.json" if a.wide_ab or a.n_var > 8 else "bench.json")
     assert torch.cuda.is_available(), "bench_pointwise needs the GPU"
     ops = [("+", None, 2, 0.5), ("-", None, 2, 0.1), ("*", None, 2, 0.5), ("/", None, 2, 0.1),
            ("sin", None, 1, 0.1), ("cos", None, 1, 0.1), ("exp", None, 1, 0.1)]
-    lib = mt.NodeLibrary(ops, [["x0", "x1"]], [1])
+    nv = a.n_var
+    assert nv >= 2 and not (a.wide_ab and (a.scaled or nv > 8)), "--wide-ab: unscaled, at most 8 columns"
+    lib = mt.NodeLibrary(ops, [[f"x{k}" for k in range(nv)]], [1])
+    ff = lambda **kw: mt.PointwiseEvaluator(MAXF, wide=nv > 8, **kw)  # noqa: E731
     pop = torch.from_numpy(sample_population(0, lib, a.P, 1, max_init_depth=10, max_nodes=63)[0]).cuda()
     rng = np.random.default_rng(1)
     lines = []
     for M in a.points:
-        X = rng.uniform(-2, 2, size=(M, 2)).astype(np.float32)
-        Y = (np.sin(X[:, :1]) * X[:, 1:]).astype(np.float32)
-        new = DeviceEngine(mt.PointwiseEvaluator(MAXF), lib, PARSIMONY, "cuda:0")
-        new_eval = DeviceEngine(mt.PointwiseEvaluator(MAXF), lib, PARSIMONY, "cuda:0")  # (keeps its built code)
-        old = DeviceEngine(_TreeOnly(1, 2), lib, 0.0, "cuda:0")
+        X = rng.uniform(-2, 2, size=(M, nv)).astype(np.float32)
+        Y = (np.sin(X[:, :1]) * X[:, -1:]).astype(np.float32)
+        new = DeviceEngine(ff(), lib, PARSIMONY, "cuda:0")
+        new_eval = DeviceEngine(ff(), lib, PARSIMONY, "cuda:0")  # (keeps its built code)
+        old = DeviceEngine(_TreeOnly(1, nv), lib, 0.0, "cuda:0")
         old.prepare_data(None)
         x_dev, y_t = torch.from_numpy(X).cuda(), torch.from_numpy(Y.T.copy()).cuda()
         fl_new, fl_old = new_eval.evaluate(pop, (X, Y))["_flat"], old.flatten(pop)
@@ -97,7 +109,7 @@ def main():
             "torch_eval": lambda: torch_fitness(old.eval_programs(fl_old, x_dev), y_t, fl_old.nodes),
         }
         if a.scaled:
-            sc = DeviceEngine(mt.PointwiseEvaluator(MAXF, linear_scaling=True), lib, PARSIMONY, "cuda:0")
+            sc = DeviceEngine(ff(linear_scaling=True), lib, PARSIMONY, "cuda:0")
             fl_sc = sc.evaluate(pop, (X, Y))["_flat"]
 
             def torch_scaled():
@@ -106,7 +118,19 @@ def main():
 
             routes = {"scaled_eval": lambda: sc.evaluate(pop, (X, Y), flattened=fl_sc, check=False)["fitness"],
                       "fused_eval": routes["fused_eval"], "torch_eval": torch_scaled}
-        first = "scaled_eval" if a.scaled else "fused_eval"
+        if a.wide_ab:  # the knob is read at every flatten, build and launch: one engine and one flattening per kernel
+            wide_eng = DeviceEngine(ff(), lib, PARSIMONY, "cuda:0")
+
+            def knob(on, fn):
+                os.environ["MTGP_PW_WIDE"] = "1" if on else "0"
+                return fn()
+
+            fl_wide = knob(True, lambda: wide_eng.evaluate(pop, (X, Y))["_flat"])
+            narrow = routes["fused_eval"]
+            routes = {"wide_eval": lambda: knob(True, lambda: wide_eng.evaluate(pop, (X, Y), flattened=fl_wide,
+                                                                                check=False)["fitness"]),
+                      "torch_eval": lambda: knob(False, narrow)}  # (reported as narrow_eval)
+        first = "scaled_eval" if a.scaled else "wide_eval" if a.wide_ab else "fused_eval"
         f_new, f_old = routes[first]().cpu().numpy(), routes["torch_eval"]().cpu().numpy()
         ms = {k: [] for k in routes}
         for r in range(a.warmup + a.reps):  # alternating: one call of every route per round
@@ -114,7 +138,7 @@ def main():
                 t = timed(fn, 1)
                 if r >= a.warmup:
                     ms[k] += t
-        line = dict(bench="pointwise", P=a.P, M=M, n_var=2, n_out=1, reps=a.reps,
+        line = dict(bench="pointwise", P=a.P, M=M, n_var=nv, n_out=1, reps=a.reps,
                     max_rel_diff=float(np.max(np.abs(f_new - f_old) / np.maximum(np.abs(f_old), 1e-30))),
                     **{f"{k}_ms": dict(median=statistics.median(v), min=min(v), max=max(v)) for k, v in ms.items()})
         if a.scaled:
@@ -122,7 +146,10 @@ def main():
             line["bench"] = "pointwise_scaled"
             line["ratio_scaled_over_unscaled"] = med["scaled_eval"] / med["fused_eval"]
             line["ratio_torch_over_scaled"] = med["torch_eval"] / med["scaled_eval"]
-        for kind in () if a.scaled else ("step", "eval"):
+        if a.wide_ab:  # (the second route is k_pointwise: max_rel_diff must be 0)
+            line["bench"], line["narrow_eval_ms"] = "pointwise_wide_ab", line.pop("torch_eval_ms")
+            line["ratio_wide_over_narrow"] = line["wide_eval_ms"]["median"] / line["narrow_eval_ms"]["median"]
+        for kind in () if a.scaled or a.wide_ab else ("step", "eval"):
             line[f"{kind}_ratio_torch_over_fused"] = line[f"torch_{kind}_ms"]["median"] / line[f"fused_{kind}_ms"]["median"]
         print(json.dumps(line), flush=True)
         lines.append(line)
@@ -130,6 +157,9 @@ def main():
         sc = fl_sc = None
         torch.cuda.empty_cache()
     os.makedirs(os.path.dirname(a.out) or ".", exist_ok=True)
+    if a.append and os.path.exists(a.out):
+        with open(a.out) as f:
+            lines = json.load(f) + lines
     with open(a.out, "w") as f:
         json.dump(lines, f, indent=1)
 
