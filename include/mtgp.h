@@ -500,7 +500,8 @@ int mtgp_eval_pointwise_jit(const MtgpPointwise* pw, const MtgpInstr* prog, cons
  *   rounded): invalid iff Sff is not finite (some f was not); cff = Sff - Sf Sf / n,
  *   cfy = Sfy - Sf Sy / n, cyy = Syy - Sy Sy / n; degenerate (f scored as a constant) iff
  *   !(cff > 2^-40 Sff): b = 0, a = Sy / n, sse = cyy; else b = cfy / cff, a = (Sy - b Sf) / n,
- *   sse = cyy - b cfy; sse = max(sse, 0);
+ *   sse = cyy - b cfy; a negative sse becomes 0, a NaN sse is kept (a non-finite target makes Sy /
+ *   Syy, so cyy, non-finite: the NaN reaches the total and the epilogue scores max_fitness);
  *   total = sse_0, + sse_d for d = 1 .. in order; any output invalid: max_fitness, else
  *   (float)(total / n); then the unscaled epilogue in f32 (non-finite -> max_fitness, clip,
  *   + parsimony * nodes[p]).  scale[p, d] = ((float)a, (float)b), ((float)(Sy / n), 0) when invalid.

@@ -3616,7 +3616,7 @@ __device__ __forceinline__ void pw_scaled_finish(const MtgpPointwise& pw, const 
       a = (Sy - b * Sf) / n;
       sse = cyy - b * cfy;
     }
-    sse = sse > 0.0 ? sse : 0.0;
+    sse = sse < 0.0 ? 0.0 : sse;  // a NaN (a non-finite target: Sy / Syy, so cyy) is kept and reaches pw_epilogue
     total = (j == 0) ? sse : total + sse;
     bad = bad || invalid;
     if (sc.scale) {

@@ -1,5 +1,7 @@
 """PointwiseEvaluator on the GPU: k_pointwise against a literal float32 restatement of include/mtgp.h's
 reduction order, float64, eval_programs, on its three program paths, and through GeneticProgramming."""
+import functools
+
 import numpy as np
 import pytest
 import torch
@@ -13,8 +15,10 @@ pytestmark = pytest.mark.gpu
 f32, MAXF = np.float32, 1e4
 
 
-def fitness_ref(pred, Y, max_fitness=MAXF):
-    """The spec in np.float32: pred [n_out, M], Y [M, n_out] -> clipped fitness (no parsimony)."""
+def fitness_ref(pred, Y, max_fitness=MAXF, left_fold=False):
+    """The spec in np.float32: pred [n_out, M], Y [M, n_out] -> clipped fitness (no parsimony).
+    left_fold: the span sums added one after the other instead -- NOT the spec: the order that
+    test_pointwise_reference.py requires the span tests' inputs to tell from the right one."""
     e = pred[0] - Y[:, 0]
     sq = e * e
     for d in range(1, pred.shape[0]):
@@ -34,6 +38,8 @@ def fitness_ref(pred, Y, max_fitness=MAXF):
             lane = lane + lane[np.arange(64) ^ w]
         parts.append(lane[0])
     v = np.array(parts + [0.0] * ((1 << (len(parts) - 1).bit_length()) - len(parts)), f32)
+    if left_fold:
+        v = np.array([functools.reduce(lambda a, b: a + b, parts)], f32)
     while len(v) > 1:  # span sums pairwise in span order
         v = v[0::2] + v[1::2]
     with np.errstate(all="ignore"):
@@ -71,6 +77,9 @@ def tree(lib, expr, N=16):
 def value(expr, X):
     if isinstance(expr, tuple):
         a, b = value(expr[1], X), value(expr[2], X)
+        if expr[0] == "/":  # IEEE division, as the kernels' (x / 0 = +-inf, 0 / 0 = NaN)
+            with np.errstate(all="ignore"):
+                return a / b
         return a + b if expr[0] == "+" else a - b if expr[0] == "-" else a * b
     return X[:, int(expr[1:])] if isinstance(expr, str) else np.full(len(X), expr, f32)
 
