@@ -3628,6 +3628,19 @@ __device__ __forceinline__ void pw_scaled_finish(const MtgpPointwise& pw, const 
   pw.fitness[p] = bad ? pw_epilogue(pw, pw.max_fitness, p) : pw_epilogue(pw, (float)(total / n), p);
 }
 
+// the interpreter on the data column dcol (slot k at dcol[k * kWave]) for the lanes `mine`: every
+// lane without usable code, else the lanes that need the slow sin/cos reduction.  (The callers form
+// `mine` next to their flag test: formed here, the JIT kernels compile to other, longer code.)
+__device__ __forceinline__ void pw_interpret(const PwArgs& A, int p, int no, bool mine,
+                                             const float* dcol, float* st, float (&f)[MTGP_PW_MAX_OUT]) {
+#pragma unroll 1
+  for (int q = 0; q < no; ++q) {
+    const float v = run_prog(A.prog + ((size_t)p * A.n_prog + q) * A.L, dcol, st);
+#pragma unroll
+    for (int j = 0; j < MTGP_PW_MAX_OUT; ++j) f[j] = (q == j && mine) ? v : f[j];
+  }
+}
+
 // the n_out programs of individual p on this wave's chunk: data d[] -> f[]
 template <bool JIT>
 __device__ __forceinline__ void pw_run(const PwArgs& A, int p, int no, bool jok, uint32_t jtab, int lane,
@@ -3652,16 +3665,10 @@ __device__ __forceinline__ void pw_run(const PwArgs& A, int p, int no, bool jok,
     }
     if (__builtin_expect(fl == 0, 1)) return;
   }
-  // the interpreter: every lane without usable code, else the lanes that need the slow sin/cos reduction
   const bool mine = !coded || ((fl >> lane) & 1ull) != 0;
 #pragma unroll
   for (int k = 0; k < kDMax; ++k) dcol[k * kWave] = d[k];
-#pragma unroll 1
-  for (int q = 0; q < no; ++q) {
-    const float v = run_prog(A.prog + ((size_t)p * A.n_prog + q) * A.L, dcol, st);
-#pragma unroll
-    for (int j = 0; j < MTGP_PW_MAX_OUT; ++j) f[j] = (q == j && mine) ? v : f[j];
-  }
+  pw_interpret(A, p, no, mine, dcol, st, f);
 }
 
 // One chunk's outputs f[] of a lane into its sums (steps 1-2 of the spec; scaled: step 1), and the
@@ -3856,12 +3863,7 @@ __device__ __forceinline__ void pw_run_lds(const PwArgs& A, int p, int no, bool 
     if (__builtin_expect(fl == 0, 1)) return;
   }
   const bool mine = !coded || ((fl >> lane) & 1ull) != 0;
-#pragma unroll 1
-  for (int q = 0; q < no; ++q) {
-    const float v = run_prog(A.prog + ((size_t)p * A.n_prog + q) * A.L, col, st);
-#pragma unroll
-    for (int j = 0; j < MTGP_PW_MAX_OUT; ++j) f[j] = (q == j && mine) ? v : f[j];
-  }
+  pw_interpret(A, p, no, mine, col, st, f);
 }
 
 // (LDS-data units clobber v8-v59, so what lives across the calls -- the staged pieces, the sums,
@@ -3946,36 +3948,20 @@ __global__ void __launch_bounds__(kPwWaves * kWave) k_pointwise_wide(PwArgs A) {
 }
 
 #if MTGP_TU_POINTWISE
-// Fitness of individuals whose M points span several waves: the W span sums combined pairwise in
-// span order (zeros up to the next power of two; a binary-counter stack as in k_rollout_mean), then
-// pw_finish.  One thread per individual.
-__global__ void __launch_bounds__(256) k_pointwise_mean(MtgpPointwise pw, int P, int W) {
-  const int p = blockIdx.x * blockDim.x + threadIdx.x;
-  if (p >= P) return;
-  int np2 = 1, top = 0;
-  while (np2 < W) { np2 <<= 1; ++top; }
-  float cst[32];
-  for (int c = 0; c < np2; ++c) {
-    float x = c < W ? pw.partials[(size_t)p * W + c] : 0.0f;
-    int lvl = 0;
-    for (; (c >> lvl) & 1; ++lvl) x = cst[lvl] + x;
-    cst[lvl] = x;
-  }
-  pw.fitness[p] = pw_finish(pw, cst[top], p);
-}
-
-// The same for linear scaling: each of the 3 n_out moments over the W span triples of
-// moments[P, W, n_out, 3], then pw_scaled_finish.  The counter's levels are unrolled (W <= 2^19
-// spans of an int32 M), so the stack stays in registers; the last span's carry chain ends in the
-// total.
+// W span values src[c * stride] combined pairwise in span order, zeros up to np2 = the next power of
+// two: a binary-counter stack as in k_rollout_mean.  Span c carries up through the set bits of c
+// (x = cst[l] + x) and is stored at the first clear bit; the last span's carry chain ends in the
+// total.  The counter's levels are unrolled (W <= 2^19 spans of an int32 M), so the stack stays in
+// registers.
 constexpr int kPwLevels = 20;
-__device__ __forceinline__ double pw_span_tree(const double* src, int stride, int W, int np2) {
-  double cst[kPwLevels], x = 0.0;
+template <class T>
+__device__ __forceinline__ T pw_span_tree(const T* src, int stride, int W, int np2) {
+  T cst[kPwLevels], x = T(0);
 #pragma unroll
-  for (int l = 0; l < kPwLevels; ++l) cst[l] = 0.0;
+  for (int l = 0; l < kPwLevels; ++l) cst[l] = T(0);
 #pragma unroll 1
   for (int c = 0; c < np2; ++c) {
-    x = c < W ? src[(size_t)c * stride] : 0.0;
+    x = c < W ? src[(size_t)c * stride] : T(0);
     bool carry = true;
 #pragma unroll
     for (int l = 0; l < kPwLevels; ++l) {
@@ -3988,6 +3974,18 @@ __device__ __forceinline__ double pw_span_tree(const double* src, int stride, in
   return x;
 }
 
+// Fitness of individuals whose M points span several waves: the span tree of the W span sums, then
+// pw_finish.  One thread per individual.
+__global__ void __launch_bounds__(256) k_pointwise_mean(MtgpPointwise pw, int P, int W) {
+  const int p = blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= P) return;
+  int np2 = 1;
+  while (np2 < W) np2 <<= 1;
+  pw.fitness[p] = pw_finish(pw, pw_span_tree(pw.partials + (size_t)p * W, 1, W, np2), p);
+}
+
+// The same for linear scaling: each of the 3 n_out moments over the W span triples of
+// moments[P, W, n_out, 3], then pw_scaled_finish.
 __global__ void __launch_bounds__(256) k_pointwise_scaled_mean(MtgpPointwise pw, MtgpPointwiseScale sc, int P, int W) {
   const int p = blockIdx.x * blockDim.x + threadIdx.x;
   if (p >= P) return;
@@ -5995,10 +5993,10 @@ int mtgp_tu_launch_pointwise(const void* A_, bool jit, bool scaled, hipStream_t 
   return launch_checked([&] {
     const size_t lds = A.chunks ? (size_t)pw_wide_lds(A.pw.n_var + A.pw.n_out, A.chunks) : 0;
     mtgp::with_flag(jit, [&](auto J) {
-      if (A.chunks && scaled) hipLaunchKernelGGL((k_pointwise_wide<J(), true>), grid, block, lds, s, A);
-      else if (A.chunks) hipLaunchKernelGGL((k_pointwise_wide<J()>), grid, block, lds, s, A);
-      else if (scaled) hipLaunchKernelGGL((k_pointwise<J(), true>), grid, block, 0, s, A);
-      else hipLaunchKernelGGL((k_pointwise<J()>), grid, block, 0, s, A);
+      mtgp::with_flag(scaled, [&](auto S) {
+        if (A.chunks) hipLaunchKernelGGL((k_pointwise_wide<J(), S()>), grid, block, lds, s, A);
+        else hipLaunchKernelGGL((k_pointwise<J(), S()>), grid, block, 0, s, A);
+      });
     });
     if (A.W > 1 && scaled) hipLaunchKernelGGL(k_pointwise_scaled_mean, mgrid, mblock, 0, s, A.pw, A.sc, A.P, A.W);
     else if (A.W > 1) hipLaunchKernelGGL(k_pointwise_mean, mgrid, mblock, 0, s, A.pw, A.P, A.W);

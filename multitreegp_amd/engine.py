@@ -204,6 +204,15 @@ class DeviceEngine:
         fl.jit_key = key + (self._arena_i, self._arena_gen[self._arena_i])
         return fl.jit
 
+    def _jit_code(self, fl: Flattened, m, R: int, order: Optional[torch.Tensor]) -> "nat.MtgpJitCode":
+        """jit_build's code as the MtgpJitCode an evaluator entry takes (left empty when disabled)."""
+        jit = self.jit_build(fl, m, R, order)
+        jc = nat.MtgpJitCode()
+        if jit is not None:
+            jc.code, jc.offsets, jc.info, jc.capacity = jit[0], jit[1].data_ptr(), jit[2].data_ptr(), jit[3]
+            jc.chain = jit[4]
+        return jc
+
     def jit_chain(self, m, n_prog: int) -> "nat.MtgpJitChain":
         """The role chain the evaluator of model struct `m` calls (mtgp_jit_chain); none when
         MTGP_JIT_CHAIN=0 (A/B switch) or in LDS-data mode."""
@@ -551,11 +560,7 @@ class DeviceEngine:
                         buf = res[name] = torch.empty((S, c, PR), dtype=torch.float32, device=dev)
                     setattr(out, name, buf.data_ptr())
         stream = torch.cuda.current_stream(dev).cuda_stream
-        jit = self.jit_build(fl, m, lanes, ro_order)
-        jc = nat.MtgpJitCode()
-        if jit is not None:
-            jc.code, jc.offsets, jc.info, jc.capacity = jit[0], jit[1].data_ptr(), jit[2].data_ptr(), jit[3]
-            jc.chain = jit[4]
+        jc = self._jit_code(fl, m, lanes, ro_order)
         rc = self.native.mtgp_eval_rk4_jit(ctypes.byref(m), fl.prog.data_ptr(), fl.plen.data_ptr(), fl.n_prog, fl.L,
                                            fl.nodes.data_ptr(), P, ctypes.byref(ro), ctypes.byref(out),
                                            ctypes.byref(jc), stream)
@@ -629,11 +634,7 @@ class DeviceEngine:
         if predictions:
             res["pred"] = torch.empty((P, n_out, M), dtype=torch.float32, device=dev)
             pw.pred = res["pred"].data_ptr()
-        jit = self.jit_build(fl, None, 64, order)
-        jc = nat.MtgpJitCode()
-        if jit is not None:
-            jc.code, jc.offsets, jc.info, jc.capacity = jit[0], jit[1].data_ptr(), jit[2].data_ptr(), jit[3]
-            jc.chain = jit[4]
+        jc = self._jit_code(fl, None, 64, order)
         stream = torch.cuda.current_stream(dev).cuda_stream
         args = (fl.prog.data_ptr(), fl.plen.data_ptr(), fl.n_prog, fl.L, P, ctypes.byref(jc), stream)
         if scaled:
